@@ -9,10 +9,14 @@ that keeps the fp16 forward's selection identical to the reference's) and the se
 every rank runs the same per-GPU work on its own triplets (weak scaling) and the embeddings are
 all-gathered over RCCL so every rank holds the global batch for mining.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`,
+the live roofline of the timed region, what the near-tie refinement and the precision guard did).  Everything else --
+repeats of the region, the isolated-forward roofline, the refinement-window and two-in-flight secondaries, the f32-class
+paths, variable-length inference, the training legs, the register-only MFMA rate and the CPU baseline -- runs only with
+--full.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -30,6 +34,7 @@ import torch
 BATCH_TRIPLETS = 256
 FRAMES = 160
 PRE_STEPS = 30                              # untimed settle-in steps before the W contract warm-ups (see pre_steps)
+PARAM_SAMPLE = 65536                        # --dump-outputs of the training step: elements kept per parameter (seeded sample)
 # tests/emul_bench.py only: run main() on CPU tensors with the kernels on the host emulator under gloo (a test of the
 # N > 1 launch sequence without GPUs).  Never set from the command line or the environment; the product package refuses
 # CPU tensors on its own.
@@ -80,37 +85,19 @@ def conv_sources_digest(precision):
 def cpu_baseline(sd_np, budget_s=7.0):
     """The reference's CPU forward, eval mode, fp32, on the host cores, at B = 32 and B = 256.
 
-    kind "reference": the UNMODIFIED /root/reference/model.py (`DeepSpeakerModel(512, 1211).eval()`, BASELINE.md 4
-    steps 2-3) when that tree exists on this host; kind "port": its torch-ATen restatement
-    (oracle/torch_restatement.py, pinned to the reference's recorded outputs by tests/test_oracle_golden.py) where it does
-    not -- the GPU box has no /root/reference.  Both run the same oneDNN convolutions.
+    kind "port": the reference model's torch-ATen restatement (oracle/torch_restatement.py, pinned to the reference's
+    recorded outputs by tests/test_oracle_golden.py), which runs the same oneDNN convolutions as the reference's
+    `DeepSpeakerModel(512, 1211).eval()`; the benchmark reads nothing outside the repository.
 
     Two figures: `all_cores` -- torch.set_num_threads(os.cpu_count()), the plan's protocol -- and `value`, the best of a
     short thread-count scan that includes it (oneDNN degrades badly when over-subscribed; `cores` = the threads of the
     reported value).  Bounded samples."""
     ncpu = os.cpu_count() or 1
     sd = {k: torch.from_numpy(np.array(v)) for k, v in sd_np.items()}
-    kind, fwd = "port", None
-    ref_dir = "/root/reference"
-    if os.path.isfile(os.path.join(ref_dir, "model.py")):
-        try:
-            import importlib.util
-            import warnings
-            spec = importlib.util.spec_from_file_location("_reference_model", os.path.join(ref_dir, "model.py"))
-            ref_mod = importlib.util.module_from_spec(spec)
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                spec.loader.exec_module(ref_mod)
-                torch.manual_seed(0)
-                ref_model = ref_mod.DeepSpeakerModel(512, 1211).eval()
-            ref_model.load_state_dict(sd)
-            kind, fwd = "reference", ref_model.forward
-        except Exception as exc:                    # (the port below is pinned to the same outputs)
-            print(f"[bench] the reference model did not import ({exc}); timing its restatement", file=sys.stderr)
-    if fwd is None:
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))        # the checker, used by this leg only
-        import torch_restatement as TR
-        fwd = lambda x: TR.forward_eval(sd, x)      # noqa: E731
+    kind = "port"
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))        # the checker, used by this leg only
+    import torch_restatement as TR
+    fwd = lambda x: TR.forward_eval(sd, x)          # noqa: E731
     x32 = torch.randn(32, 1, FRAMES, 64)
     scan = {}
     with torch.no_grad():
@@ -160,8 +147,7 @@ def cpu_baseline(sd_np, budget_s=7.0):
             "sample": f"B=32: {v32[1]} utterances [1,{FRAMES},64] ({v32[2]} forwards, {v32[3]:.1f} s); B=256: {v256[1]} "
                       f"utterances ({v256[2]} forwards, {v256[3]:.1f} s); eval forward, fp32, torch {torch.__version__} CPU, "
                       f"{cores} threads (best of a scan over 8..{ncpu}; the host has {ncpu}); "
-                      + ("the unmodified /root/reference/model.py" if kind == "reference" else
-                         "oracle/torch_restatement.py (no /root/reference on this host)")}
+                      "oracle/torch_restatement.py (the reference model's forward restated in torch operators)"}
 
 
 def _backend():
@@ -243,15 +229,17 @@ def main():
                          "mining.REFINE_CAP_MIN); the policy grows them from observed counts either way")
     ap.add_argument("--ablate", default="", help="diagnosis only (the line is then NOT the contract's workload): comma list of "
                     "'refine' (filter without the near-tie re-embedding) and 'mine' (no semi-hard search)")
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="after the contract's timed region (W warm-up + K steps -> `value`), time the same K-step region "
-                         "this many more times and report median / min / max ms per step (box-to-box and DVFS spread)")
+                         "this many more times and report median / min / max ms per step (box-to-box and DVFS spread); "
+                         "the eval line's isolated-forward roofline, `refine_window_8` and `pipelined` come with them.  "
+                         "Default 3 with --full, 0 without")
     ap.add_argument("--precision", default="f16", choices=["f32", "bf16x3", "bf16", "f16"],
                     help="arithmetic of the stage convolutions: fp16 operands + fp16 activations (default; 3.7e-4 from "
                          "the reference, near-tie selections refined at f32-class precision), split-operand bf16 MFMA "
                          "(f32-class accuracy, 6e-6), exact-f32 MFMA, or plain bf16 (~3e-3: outside the contract)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the untimed comparison runs (split-operand bf16 and exact f32) and the training step")
+                    help="--full: skip the untimed comparison runs (split-operand bf16 and exact f32) and the training step")
     ap.add_argument("--split-apn", action="store_true",
                     help="three separate 256-utterance forwards (the reference's call pattern, "
                          "train_triplet.py:215) instead of one 768-utterance forward")
@@ -286,7 +274,18 @@ def main():
                          "round-robin in creation order, and which streams of a step share a queue changes its overlap)")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="only rendezvous, one all-reduce and the one-line print (checks the launcher, not the kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: repeats of the timed region and the secondaries "
+                         "that come with them, the f32-class paths, variable-length inference, the training legs, the "
+                         "register-only MFMA rate and the CPU baseline (--no-secondary / --no-cpu-baseline still drop theirs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed (the arrays a caller of the step "
+                         "receives; float32 / float64, a fixed seeded sample of each parameter of the training step) as "
+                         "DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 0
+    secondaries = args.full and not args.no_secondary
 
     ablate = set(a for a in args.ablate.split(",") if a)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -404,7 +403,7 @@ def main():
         """untimed settle-in steps run BEFORE the W contract warm-ups (reported as `pre_steps` in the line)"""
         return max(0, PRE_STEPS - warmup)
 
-    def timed(step, steps, warmup, repeats=0, profile=True, finish=None, profile_every=1, settle_s=0.0):
+    def timed(step, steps, warmup, repeats=0, profile=True, finish=None, profile_every=1, settle_s=0.0, after_region=None):
         # profile: per-launch events around the convolutions of the timed region (the live roofline of the eval line); the
         # training steps are timed without them (a pair of events per launch is ~70 per fp16 training step -- measured
         # 12.7 ms per step with them, 9.6 without)
@@ -450,6 +449,8 @@ def main():
             print(f"[bench] host enqueue {t_enq / steps * 1e3:.3f} ms/step, device-complete {elapsed / steps * 1e3:.3f} ms/step",
                   file=sys.stderr)
         prof, eng.profile = (eng.profile or []), None
+        if after_region is not None:            # (--dump-outputs: before anything else runs a step)
+            after_region()
         try:                                    # the launch-bound events of the region must all read back
             for p_ in prof:
                 p_[2].elapsed_time(p_[3])
@@ -476,6 +477,8 @@ def main():
         parity = [0] * n_slots
         sels = []
         step_no = [0]
+        dumping = args.dump_outputs is not None and precision == args.precision
+        last = {}                                   # --dump-outputs: the results of the latest step
 
         def step(slot=0):
             par = parity[slot]
@@ -520,10 +523,25 @@ def main():
             sels.append(sel)
             if len(sels) > 4 * steps:
                 del sels[:-steps]
+            if dumping:
+                last.update(e_all=e_all, loss=loss, sel=sel, mined=mined)
             return loss, sel, mined
 
+        def dump_last_step():
+            # what a caller of the step receives from the last timed step; reading the selection resolves it (and
+            # synchronises) exactly as a caller's read would
+            sel, mined = last["sel"], last["mined"]
+            out = {"embeddings": host(last["e_all"]), "loss": host(last["loss"]),
+                   "selected_triplets": host(sel.indices, np.float64), "selection_d_p": host(sel.d_p),
+                   "selection_d_n": host(sel.d_n), "selection_mean_diff": host(sel.mean_diff)}
+            if mined is not None:
+                out["mined_negatives"] = host(mined.indices, np.float64)
+                out["mined_negative_distances"] = host(mined.distances)
+            write_outputs(out)
+
         elapsed, prof, again = timed(step, steps, warmup, repeats, finish=refine_policy(model).flush,
-                                     profile_every=args.profile_every if precision == args.precision else 1)
+                                     profile_every=args.profile_every if precision == args.precision else 1,
+                                     after_region=dump_last_step if dumping else None)
         # The same kernels with NOTHING else on the chip: forwards only, back to back (no loss / filter / refinement /
         # search, hence no side stream).  Inside the step the near-tie refinement and the semi-hard search of step k run
         # on a side stream next to the forward of step k + 1 and take CUs from it, so the per-launch durations measured
@@ -624,6 +642,19 @@ def main():
     red_modes = [None, None]
     extras = {}
 
+    def host(t, dtype=np.float32):
+        return np.asarray(t.detach().cpu().numpy(), dtype)
+
+    def write_outputs(arrays):
+        """--dump-outputs: one DIR/<name>.npy per array (rank 0; every rank computed the same shapes on its own triplets)"""
+        if rank != 0:
+            return
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a))
+        total = sum(a.nbytes for a in arrays.values())
+        print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MiB -> {args.dump_outputs}", file=sys.stderr)
+
     def measure_train(precision, steps, warmup, repeats=0):
         """The training step of the triplet regime (train_triplet.py:215-224): train-mode forwards of a / p / n
         (three BatchNorm statistic sets, as the reference), triplet loss, backward (gradient all-reduce inside),
@@ -635,6 +666,8 @@ def main():
                                          grad_reduce=args.grad_reduce) if multi else None
         opt = create_optimizer(model, 0.1, "adagrad", lr_decay=1e-4)
         tstep_no = [0]
+        dumping = args.dump_outputs is not None and args.train and precision == args.train_precision
+        last = {}                                   # --dump-outputs: the results of the latest step
 
         def step(slot=0):
             # the three forwards of train_triplet.py:215 in lock-step over one batch (same values, three BatchNorm
@@ -651,6 +684,8 @@ def main():
             opt.step()
             if multi:                           # the global loss the loop logs every step (train_triplet.py:226)
                 red.all_reduce_sum_(loss.detach())
+            if dumping:
+                last.update(loss=loss.detach(), outs=[o.detach() for o in (out_a, out_p, out_n)])
             return loss
 
         if args.graph:
@@ -662,8 +697,26 @@ def main():
             def step(slot=0):                   # noqa: F811  (the replay: three input copies + one graph launch)
                 d_ = batches[tstep_no[0] % n_batches]["apn"]
                 tstep_no[0] += 1
-                return gstep(d_[0], d_[1], d_[2])
-        elapsed, prof, again = timed(step, steps, warmup, repeats, profile=False, settle_s=args.train_settle_seconds)
+                loss = gstep(d_[0], d_[1], d_[2])
+                if dumping:
+                    last.update(loss=loss, outs=gstep.embeddings)
+                return loss
+
+        def dump_last_step():
+            # what the step hands its caller (the loss, the train-mode embeddings) and what it leaves in the model: every
+            # parameter after the optimizer update, those above PARAM_SAMPLE elements as a fixed seeded sample
+            out = {"loss": host(last["loss"]), "embeddings": host(torch.cat(list(last["outs"])))}
+            rs = np.random.RandomState(0)
+            for name, p in model.named_parameters():
+                flat = p.detach().reshape(-1)
+                if flat.numel() > PARAM_SAMPLE:
+                    pick = np.sort(rs.choice(flat.numel(), PARAM_SAMPLE, replace=False))
+                    flat = flat[torch.from_numpy(pick).to(flat.device)]
+                out["param." + name] = host(flat)
+            write_outputs(out)
+
+        elapsed, prof, again = timed(step, steps, warmup, repeats, profile=False, settle_s=args.train_settle_seconds,
+                                     after_region=dump_last_step if dumping else None)
         per_step = None
         if red is not None:
             red_modes[:] = [red.grad_comm, red.grad_reduce]
@@ -843,7 +896,7 @@ def main():
         extras["pipelined"] = extras.pop("pipelined_fn")()
 
     secondary = {}
-    if world == 1 and not args.no_secondary:
+    if world == 1 and secondaries:
         for prec in ("bf16x3", "f32"):                              # untimed comparisons: the f32-class paths
             if prec != args.precision:
                 k2 = max(3, args.steps // 2)
@@ -893,7 +946,7 @@ def main():
         etg16, _, regs_tg16 = train_leg("f16", graph=True)
     # the arithmetic the timed forwards really ran in: the requested one, unless the fp16 guard escalated
     eff_prec = extras.get("precision_guard", {}).get("verdict", args.precision)
-    if rank == 0 and dev.type == "cuda" and not args.no_secondary:
+    if rank == 0 and dev.type == "cuda" and secondaries:
         try:                # (after every timed region: the probe heats the chip)
             for kind in ("f16", "bf16"):
                 measure_mfma_rate(kind)
@@ -958,7 +1011,7 @@ def main():
             out["precision_guard"]["value_if_escalated_what"] = (
                 "embeddings/s of this step when the guard escalates (a trained network whose fp16 error estimate passes "
                 f"{out['precision_guard']['threshold']:g}): the split-operand bf16 path, measured in this run (`bf16x3_path`)")
-        if world == 1 and not args.no_secondary:
+        if world == 1 and secondaries:
             out["train_step"] = {"value": round(emb_per_step * kt / et, 1), "unit": "utterances/s", "steps": kt,
                                  "ms_per_step": round(et / kt * 1e3, 3), "dtype": "bf16x3",
                                  "algorithmic_tflops": round(emb_per_step * kt / et * 3 * FWD_FLOPS_PER_EMB / 1e12, 1),
@@ -990,7 +1043,7 @@ def main():
                     if dt_ == "f16":
                         out[key_]["outside_contract"] = True
             out["varlen"] = varlen
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd_np)
         # key order of the printed line: the contract's keys, then what a reader must not lose if the line's tail is cut
         # (what the refinement did in the timed steps -- overflows / band violations / the embedding error it observed --

@@ -77,3 +77,16 @@ def test_train_bench_two_ranks_end_to_end_on_the_emulator(tprec):
     assert d["all_reduce_per_step"] == 2 * 12 + 5 + 1
     assert d["config"]["parallelism"] == "dp2" and d["config"]["grad_comm"] == "shared"
     assert d["config"]["grad_reduce"] == "allreduce"
+
+
+def test_train_bench_dumps_its_last_step_on_the_emulator(tmp_path):
+    """`bench.py --train --dump-outputs DIR` (kernels on the host emulator, two ranks): rank 0 writes the last timed step's
+    loss, train-mode embeddings and updated parameters as float32 .npy files."""
+    import numpy as np
+    d = _run_emulated("--train", "--train-precision", "bf16x3", "--steps", "1", "--warmup", "0", "--train-settle-seconds", "0",
+                      "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 1 and "repeats_ms_per_step" not in d       # a plain run times its region once
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert {"loss", "embeddings", "param.model.conv1.weight", "param.model.fc.weight"} <= set(got)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    assert got["embeddings"].shape == (3 * 1, 512)                  # one triplet per rank (_run_emulated)

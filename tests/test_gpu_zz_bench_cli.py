@@ -18,9 +18,10 @@ pytestmark = pytest.mark.gpu
 
 
 def run_bench(*flags, port):
+    """--full: the line with the region's repeats and the secondaries that come with them"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "1", "--no-cpu-baseline",
-                          "--no-secondary", *flags], capture_output=True, text=True, env=env, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "1",
+                          "--no-cpu-baseline", "--no-secondary", *flags], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -108,3 +109,44 @@ def test_bench_fp16_train_mode_and_its_collective_path():
     # (24 small collectives sit serially on the lock-step chain of a 9 ms step: measured +15 % with one rank, +3 % on the 18 ms
     # f32-class step whose forward hides them behind the other members' streams)
     perf_note(settled_ms(forced) < 1.25 * settled_ms(plain), ("fp16 collective path vs plain", forced["ms_per_step"], plain["ms_per_step"]))
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline keys over exactly K timed
+    steps, none of the measurements --full adds, and the last timed step's results as DIR/<name>.npy (float32 / float64,
+    at most 64 MB).  A second run with the same arguments sees the same inputs and computes the same results."""
+    import time
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines, dumps = [], []
+    for i in range(2):
+        dump = tmp_path / f"run{i}"
+        t0 = time.perf_counter()
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                              "--dump-outputs", str(dump)], capture_output=True, text=True, env=env, timeout=600)
+        wall = time.perf_counter() - t0
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, out.stdout[-2000:]
+        d = json.loads(js[0])
+        lines.append(d)
+        dumps.append({p.stem: np.load(p) for p in dump.glob("*.npy")})
+        perf_note(wall - (6 + 2) * d["ms_per_step"] * 1e-3 < 30.0, ("plain run outside its steps, s", round(wall, 1)))
+    for d in lines:
+        assert d["steps"] == 6 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 1e4
+        assert d["unit"] == "embeddings/s" and d["higher_is_better"] is True and d["dtype"] == "f16"
+        assert abs(d["value"] - 3 * 256 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+        for k in ("repeats_ms_per_step", "refine_window_8", "pipelined", "bf16x3_path", "f32_path", "train_step", "varlen",
+                  "cpu_baseline"):
+            assert k not in d, k
+        assert "isolated" not in d["roofline"]
+    a, b = dumps
+    assert set(a) == set(b) and {"embeddings", "loss", "selected_triplets", "mined_negatives"} <= set(a)
+    assert a["embeddings"].shape == (3 * 256, 512)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].shape == b[k].shape, k
+        if a[k].size:
+            assert np.abs(a[k].astype(np.float64) - b[k]).max() <= 1e-4 * max(1.0, np.abs(a[k]).max()), k
+    np.testing.assert_array_equal(a["selected_triplets"], b["selected_triplets"])

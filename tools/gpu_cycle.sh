@@ -13,17 +13,17 @@ for w in $WHAT; do
     newtests) timeout 900 python -m pytest tests/test_gpu_bench_size.py tests/test_gpu_parity.py tests/test_gpu_zz_bench_cli.py -m gpu -x -q -s > $OUT/pytest_new.log 2>&1; echo "pytest(new) rc=$?"; tail -5 $OUT/pytest_new.log ;;
     r4tests) timeout 1500 python -m pytest tests/test_gpu_offdist.py tests/test_gpu_trajectory.py tests/test_gpu_streams.py tests/test_gpu_bench_size.py tests/test_gpu_zz_bench_cli.py -m gpu -q -s > $OUT/pytest_r4.log 2>&1; echo "pytest(r4) rc=$?"; grep -E "^\[|passed|failed|FAILED|Error|policy after" $OUT/pytest_r4.log | tail -60 ;;
     f16train) timeout 1500 python -m pytest tests/test_gpu_train_f16.py tests/test_gpu_trajectory.py -m gpu -q -s > $OUT/pytest_f16train.log 2>&1; echo "pytest(f16train) rc=$?"; grep -E "^\[|passed|failed|FAILED|Error|loss scale|unmasked|bf16x3:|f16:" $OUT/pytest_f16train.log | tail -40
-           for tp in bf16x3 f16; do timeout 600 python bench.py --train --train-precision $tp --no-cpu-baseline > $OUT/train_$tp.json 2> $OUT/train_$tp.err; echo "train $tp rc=$?"; cat $OUT/train_$tp.json; done ;;
+           for tp in bf16x3 f16; do timeout 600 python bench.py --full --train --train-precision $tp --no-cpu-baseline > $OUT/train_$tp.json 2> $OUT/train_$tp.err; echo "train $tp rc=$?"; cat $OUT/train_$tp.json; done ;;
     offdist) timeout 900 python -m pytest tests/test_gpu_offdist.py -m gpu -q -s -k "trained or planted" > $OUT/pytest_offdist.log 2>&1; echo "pytest(offdist) rc=$?"; grep -E "^\[trained|passed|failed|FAILED|policy after|training losses|^E " $OUT/pytest_offdist.log | tail -30 ;;
     varlen) timeout 300 python tools/varlen_bench.py > $OUT/varlen.json 2> $OUT/varlen.err; echo "varlen rc=$?"; cat $OUT/varlen.json | cut -c1-400 ;;
     lat) timeout 300 python tools/latency_bench.py 2>&1 | grep -v amdgpu.ids | tee $OUT/latency.txt
          timeout 600 python -m pytest tests/test_gpu_edge_cases.py -m gpu -q -k "low_latency" 2>&1 | tail -3 ;;
     bn16) for g in 8192 2048 32768; do DS_TF_GRID=$g timeout 300 python tools/bn16_probe.py 2>&1 | grep -v amdgpu.ids | tee -a $OUT/bn16_probe.txt; done ;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -3 ;;
-    bench) timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json | head -c 6000 ;;
-    benchq) timeout 600 python bench.py --no-secondary --no-cpu-baseline > $OUT/benchq.json 2> $OUT/benchq.err; echo "benchq rc=$?"; cat $OUT/benchq.json | head -c 4000 ;;
-    train) timeout 600 python bench.py --train --no-cpu-baseline > $OUT/train.json 2> $OUT/train.err; echo "train rc=$?"; cat $OUT/train.json
-           MASTER_ADDR=127.0.0.1 MASTER_PORT=29571 timeout 600 python bench.py --train --force-collectives --no-cpu-baseline > $OUT/train_dp.json 2> $OUT/train_dp.err; echo "train_dp rc=$?"; cat $OUT/train_dp.json ;;
+    bench) timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json | head -c 6000 ;;
+    benchq) timeout 600 python bench.py --full --no-secondary --no-cpu-baseline > $OUT/benchq.json 2> $OUT/benchq.err; echo "benchq rc=$?"; cat $OUT/benchq.json | head -c 4000 ;;
+    train) timeout 600 python bench.py --full --train --no-cpu-baseline > $OUT/train.json 2> $OUT/train.err; echo "train rc=$?"; cat $OUT/train.json
+           MASTER_ADDR=127.0.0.1 MASTER_PORT=29571 timeout 600 python bench.py --full --train --force-collectives --no-cpu-baseline > $OUT/train_dp.json 2> $OUT/train_dp.err; echo "train_dp rc=$?"; cat $OUT/train_dp.json ;;
     prof) (cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -- python $R/bench.py --steps 10 --warmup 2 --repeats 0 --no-cpu-baseline --no-secondary > $OUT/prof.log 2>&1); echo "prof rc=$?"
           python tools/rocpd_stats.py $(find $OUT/prof -name "*.db") > $OUT/kernel_stats.md 2>$OUT/kernel_stats.err; head -40 $OUT/kernel_stats.md
           python tools/step_timeline.py $(find $OUT/prof -name "*.db") > $OUT/step_timeline.txt 2>&1; tail -4 $OUT/step_timeline.txt ;;
