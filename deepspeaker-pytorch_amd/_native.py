@@ -182,6 +182,12 @@ _SIGNATURES = {
     "ds_triplet_margin_bwd_f32": (c_int, [_P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, _P]),
     "ds_l2norm_scale_bwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, _P]),
     "ds_avgpool_time_bwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "ds_fbank_plan": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "ds_fbank_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
+    "ds_fbank_logmel_f32": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    _P, _P, _P]),
+    "ds_fbank_preemphasis_f32": (c_int, [_P, c_int, c_longlong, _P, _P]),
+    "ds_fbank_normalize_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 

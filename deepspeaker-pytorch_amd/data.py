@@ -36,6 +36,19 @@ class FeatureStore:
         self.n_feat = f
         self.features = torch.from_numpy(np.ascontiguousarray(np.concatenate(utterances, 0), dtype=np.float32)).to(device)
 
+    @classmethod
+    def from_waveforms(cls, waveforms, config=None, normalize="mean", lengths=None) -> "FeatureStore":
+        """The resident corpus straight from audio: `features.log_mel_fbank` of the waveforms (a sequence of 1-D float32
+        / int16 device tensors, or one packed tensor with host `lengths`), kept where it was computed -- no host copy."""
+        from .features import FbankConfig, log_mel_fbank
+        feats, offsets = log_mel_fbank(waveforms, FbankConfig() if config is None else config, normalize=normalize,
+                                       lengths=lengths)
+        store = cls.__new__(cls)
+        store.offsets = offsets
+        store.n_feat = feats.shape[1]
+        store.features = feats
+        return store
+
     def __len__(self):
         return len(self.offsets) - 1
 

@@ -1,0 +1,171 @@
+"""Log-mel filterbank front end on the device: waveforms -> the [T, 64] features the model consumes.
+
+The reference makes its features offline, one utterance at a time, in float64 NumPy (`mk_MFB`,
+audio_processing.py:9-36, run over the corpus by train_triplet.py --makemfb): `python_speech_features.fbank` with
+nfilt=64, winlen=0.025 (pre-emphasis 0.97, rectangular window, 512-point power spectrum, triangular mel filters), then
+20*log10(max(fb, 1e-5)) and `normalize_frames` (per filter over the utterance: subtract the mean; with use_scale also
+divide by std + 2e-12).  Here the whole batch is one HIP call chain (csrc/fbank.hip): the DFT runs as an f32 MFMA GEMM
+against a cos/sin basis built once per configuration, and the result is packed [sum T_u, nfilt] f32 on the device,
+ready for `data.FeatureStore.from_waveforms`.  Frame counts follow from the host-side lengths: no read-back.
+"""
+from __future__ import annotations
+
+import decimal
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from .model import get_engine
+
+_engine_override = None
+_NORMALIZE = ("mean", "mean_std", None)
+
+
+def _eng():
+    return _engine_override if _engine_override is not None else get_engine()
+
+
+def _round_half_up(x: float) -> int:
+    """python_speech_features.sigproc.round_half_up"""
+    return int(decimal.Decimal(x).quantize(decimal.Decimal("1"), rounding=decimal.ROUND_HALF_UP))
+
+
+@dataclass(frozen=True)
+class FbankConfig:
+    """The knobs of mk_MFB; the defaults are the reference's constants.py (SAMPLE_RATE=16000, FILTER_BANK=64,
+    USE_LOGSCALE=True) and python_speech_features' own (winstep=0.01, nfft=512)."""
+    sample_rate: int = 16000
+    nfilt: int = 64
+    nfft: int = 512
+    winlen: float = 0.025
+    winstep: float = 0.01
+    use_logscale: bool = True
+
+    @property
+    def frame_len(self) -> int:
+        return _round_half_up(self.winlen * self.sample_rate)
+
+    @property
+    def frame_step(self) -> int:
+        return _round_half_up(self.winstep * self.sample_rate)
+
+
+def mel_filterbank(config: FbankConfig) -> np.ndarray:
+    """[nfilt, nfft/2+1] float64 triangular filters of python_speech_features.get_filterbanks (lowfreq 0, highfreq
+    sample_rate/2)."""
+    nfilt, nfft, sr = config.nfilt, config.nfft, config.sample_rate
+    hz2mel = lambda hz: 2595 * np.log10(1 + hz / 700.0)
+    mel2hz = lambda mel: 700 * (10 ** (mel / 2595.0) - 1)
+    pts = np.linspace(hz2mel(0), hz2mel(sr / 2), nfilt + 2)
+    b = np.floor((nfft + 1) * mel2hz(pts) / sr)
+    fb = np.zeros((nfilt, nfft // 2 + 1))
+    for j in range(nfilt):
+        for i in range(int(b[j]), int(b[j + 1])):
+            fb[j, i] = (i - b[j]) / (b[j + 1] - b[j])
+        for i in range(int(b[j + 1]), int(b[j + 2])):
+            fb[j, i] = (b[j + 2] - i) / (b[j + 2] - b[j + 1])
+    return fb
+
+
+def dft_basis(frame_len: int, nfft: int) -> np.ndarray:
+    """[frame_len rounded up to even, nfft] float32 basis in the kernel's column order: for bin k = 32p + j, column
+    64p + j is cos(2 pi n k / nfft) and column 64p + 32 + j is sin(...), except column 32 (sin_0 = 0), which holds the
+    Nyquist bin's cos.  Built in float64 with the argument reduced exactly ((n k) mod nfft), rounded once."""
+    kpad = (frame_len + 1) & ~1
+    n = np.arange(frame_len, dtype=np.int64)[:, None]
+    p, j = np.divmod(np.arange(nfft // 2), 32)
+    k = 32 * p + j
+    col_c = 64 * p + j
+    col_s = 64 * p + 32 + j
+    ang = lambda kk: 2.0 * np.pi * ((n * kk[None, :]) % nfft) / nfft
+    basis = np.zeros((kpad, nfft), np.float64)
+    basis[:frame_len, col_c] = np.cos(ang(k))
+    basis[:frame_len, col_s] = np.sin(ang(k))
+    basis[:frame_len, 32] = np.cos(ang(np.array([nfft // 2])))[:, 0]
+    return basis.astype(np.float32)
+
+
+_tables = {}
+
+
+def _device_tables(config: FbankConfig, device: torch.device):
+    """(basis, band, weights, wstride) on `device`, built once per configuration."""
+    key = (config.frame_len, config.nfft, config.nfilt, config.sample_rate, str(device))
+    hit = _tables.get(key)
+    if hit is None:
+        fb = mel_filterbank(config).astype(np.float32)
+        nz = [np.nonzero(row)[0] for row in fb]
+        band = np.array([[r[0], r[-1] - r[0] + 1] if len(r) else [0, 0] for r in nz], np.int32)
+        wstride = max(1, int(band[:, 1].max()))
+        w = np.zeros((config.nfilt, wstride), np.float32)
+        for f, (b0, cnt) in enumerate(band):
+            w[f, :cnt] = fb[f, b0:b0 + cnt]
+        hit = (torch.from_numpy(dft_basis(config.frame_len, config.nfft)).to(device),
+               torch.from_numpy(band).to(device), torch.from_numpy(w).to(device), wstride)
+        _tables[key] = hit
+    return hit
+
+
+def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config: FbankConfig = FbankConfig(),
+                  normalize: Optional[str] = "mean", lengths: Optional[Sequence[int]] = None
+                  ) -> Tuple[torch.Tensor, np.ndarray]:
+    """mk_MFB of every waveform in one call chain on the waveforms' device.
+
+    `waveforms`: a sequence of 1-D tensors (float32 samples, or int16 PCM, which is scaled by 1/32768), or ONE packed
+    1-D tensor with the host `lengths` of its utterances.  `normalize`: "mean" (the reference's USE_SCALE=False),
+    "mean_std" (USE_SCALE=True) or None (raw log filterbank; with config.use_logscale=False the raw filterbank).
+    Returns the packed [sum T_u, nfilt] float32 features on the device and the host int64 frame offsets [n_utt + 1]:
+    utterance u is rows offsets[u]:offsets[u+1].  Deltas, resampling and decoding are the caller's."""
+    if normalize not in _NORMALIZE:
+        raise ValueError(f"normalize must be one of {_NORMALIZE}, got {normalize!r}")
+    eng = _eng()
+    if isinstance(waveforms, torch.Tensor):
+        if lengths is None or waveforms.dim() != 1:
+            raise ValueError("a packed waveform tensor must be 1-D and come with the host `lengths` of its utterances")
+        packed = waveforms.contiguous()
+        lens = np.asarray(lengths, np.int64)
+        if lens.ndim != 1 or int(lens.sum()) != packed.numel():
+            raise ValueError("lengths must sum to the packed tensor's length")
+    else:
+        if lengths is not None:
+            raise ValueError("lengths are implied by a sequence of waveforms")
+        if len(waveforms) == 0:
+            raise ValueError("no waveforms")
+        if any(w.dim() != 1 for w in waveforms) or len({w.dtype for w in waveforms}) != 1:
+            raise ValueError("waveforms must be 1-D tensors of one dtype")
+        lens = np.array([w.numel() for w in waveforms], np.int64)
+        packed = waveforms[0].contiguous() if len(waveforms) == 1 else torch.cat(list(waveforms))
+    if packed.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"waveforms must be float32 or int16, got {packed.dtype}")
+    dev = packed.device
+    n_utt = len(lens)
+    fl, fs, nfft, nfilt = config.frame_len, config.frame_step, config.nfft, config.nfilt
+
+    # framing on the host (the lengths are host data): frame counts, offsets and the tile table
+    counts = np.zeros(3, np.int64)
+    lens_c = np.ascontiguousarray(lens)
+    plan = lambda table: eng.lib.call("ds_fbank_plan", lens_c.ctypes.data, n_utt, fl, fs, nfft, nfilt,
+                                      None if table is None else table.ctypes.data, counts.ctypes.data)
+    plan(None)
+    n_frames, n_tiles, tile_rows = (int(v) for v in counts)
+    table = np.zeros(3 * (n_utt + 1) + n_tiles, np.int64)
+    plan(table)
+    offsets = table[n_utt + 1:2 * (n_utt + 1)].copy()
+    table_t = torch.from_numpy(table)
+    # through pinned memory, without blocking the host (a pageable copy waits for the stream's queue)
+    table_dev = table_t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else table_t
+
+    basis, band, weights, wstride = _device_tables(config, dev)
+    out = torch.empty((n_frames, nfilt), dtype=torch.float32, device=dev)
+    ws_bytes = int(eng.lib.raw("ds_fbank_workspace_bytes")(n_utt, n_tiles, nfilt))
+    workspace = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    stream = eng._stream(out)
+    eng.lib.call("ds_fbank_logmel_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, eng._p(table_dev),
+                 n_utt, n_tiles, eng._p(basis), eng._p(band), eng._p(weights), wstride, fl, fs, nfft, nfilt,
+                 1 if config.use_logscale else 0, eng._p(out), eng._p(workspace), stream)
+    if normalize is not None:
+        eng.lib.call("ds_fbank_normalize_f32", eng._p(out), eng._p(table_dev), n_utt, n_tiles, nfilt, tile_rows,
+                     1 if normalize == "mean_std" else 0, eng._p(workspace), stream)
+    return out, offsets

@@ -85,7 +85,8 @@ extern "C" {
 int ds_version(void);            /* 100: round 1; 200: round 2 (fp16 path, grouped BatchNorm backward, ds_bn_bwd_partial_rows takes C);
                                     300 / 301: round 3 (persistent fp16 kernels, split grouped BatchNorm backward; + ds_conv_dgrad_bnbwd_bf16);
                                     400: round 4 (fp16 training step: ds_*_f16 train entry points, ds_wgrad_f16, probes of the
-                                    near-tie refinement, launch-bound timing); 500: round 5 */
+                                    near-tie refinement, launch-bound timing); 500: round 5; 600: round 6 (caller-owned
+                                    scheduler workspace); 700: log-mel filterbank front end (ds_fbank_*) */
 /* launch timing without marker packets: the next MFMA convolution / filter-gradient launch of the calling thread
  * records its own execution into the armed pair (hipExtLaunchKernelGGL); ds_launch_timing_end() disarms and returns
  * how many such launches happened since arming (1 = the timed call was a single kernel) */
@@ -628,6 +629,36 @@ int ds_adam_step_f32(const void *params, const void *grads, const void *state1, 
  * ds_nonfinite_flag_f32: *flag = 1 if any of x[0..n) is inf or NaN (never cleared here: the tensors of one step
  * accumulate into one flag the caller zeroed). */
 int ds_nonfinite_flag_f32(const float *x, long long n, int *flag, void *stream);
+
+/* ---- log-mel filterbank front end (fbank.hip): waveforms -> [T_u, nfilt] f32 features, the reference's mk_MFB
+ * (python_speech_features.fbank with a rectangular window, pre-emphasis 0.97, then 20*log10(max(fb, 1e-5)) and
+ * normalize_frames).  Utterances are packed end to end; every buffer is the caller's.
+ * ds_fbank_plan (HOST): from the host sample counts `lengths[n_utt]`, the frame counts and the tile table.  With
+ *   table == NULL only counts[3] = {total frames, tiles, frames per tile} is written; otherwise also the int64 table
+ *   samp_off[n_utt+1] | frame_off[n_utt+1] | tile_off[n_utt+1] | tile_utt[tiles] (3 * (n_utt + 1) + tiles entries),
+ *   which the caller copies to the device.  An empty signal is DS_ERR_BAD_SHAPE; frame_len > nfft, nfft not a power of
+ *   two in 64..1024, nfilt not a multiple of 4 in 4..128, or a tile that does not fit the LDS is DS_ERR_UNSUPPORTED.
+ * ds_fbank_workspace_bytes: the f64 workspace: per-tile partial sums [tiles][2][nfilt], then per-utterance statistics
+ *   [n_utt][2][nfilt].
+ * ds_fbank_logmel_f32: samples f32 (in_int16 = 0) or int16 PCM scaled by 1/32768 (in_int16 = 1); table (device) from
+ *   ds_fbank_plan; basis [frame_len rounded up to even][nfft] f32 with column 64p + j = cos(2 pi n k / nfft) and
+ *   64p + 32 + j = sin(...) for bin k = 32p + j (column 32 holds cos of the Nyquist bin instead of sin_0); band
+ *   [nfilt][2] int32 = {first bin, count} and mel_w [nfilt][wstride] f32 the filters' nonzero weights.  out
+ *   [frames][nfilt] f32: 20*log10(max(fb, 1e-5)) (log_scale != 0) or fb; the workspace receives the tiles' partials.
+ * ds_fbank_normalize_f32: after ds_fbank_logmel_f32 on the same stream and workspace: per utterance and filter, the mean
+ *   over its frames is subtracted (use_scale: and the result divided by std + 2e-12, population std), in place.
+ *   Deterministic: partials are reduced in a fixed order, so an utterance's features do not depend on its batch. */
+int ds_fbank_plan(const long long *lengths, int n_utt, int frame_len, int frame_step, int nfft, int nfilt, long long *table,
+                  long long *counts);
+long long ds_fbank_workspace_bytes(int n_utt, int n_tiles, int nfilt);
+int ds_fbank_logmel_f32(const void *samples, int in_int16, const long long *table, int n_utt, int n_tiles,
+                        const float *basis, const int *band, const float *mel_w, int wstride, int frame_len,
+                        int frame_step, int nfft, int nfilt, int log_scale, float *out, double *workspace, void *stream);
+/* the kernels' pre-emphasis of one signal of n samples alone (y[0] = x[0], y[i] = x[i] - 0.97 x[i-1] in f32 with two
+ * roundings): a test hook for the staging arithmetic */
+int ds_fbank_preemphasis_f32(const void *samples, int in_int16, long long n, float *out, void *stream);
+int ds_fbank_normalize_f32(float *feat, const long long *table, int n_utt, int n_tiles, int nfilt, int tile_rows,
+                           int use_scale, double *workspace, void *stream);
 
 #ifdef __cplusplus
 }
