@@ -144,6 +144,11 @@ def trace_range(name: str) -> _Range:
     return _Range(name)
 
 
+def _clip_flags(residual) -> int:
+    """epilogue flags of a train-mode normalise pass: clip, plus the residual add where there is one"""
+    return DS_EPI_CLIP | (DS_EPI_RESIDUAL if residual is not None else 0)
+
+
 class Engine:
     PLAN_CACHE_ENTRIES = 64            # eval launch plans kept (each owns its activation buffers), LRU
     PLAN_CACHE_BYTES = 12 << 30        # ... and their total size (a 768 x 160-frame f32-class plan is 3.3 GiB)
@@ -425,11 +430,7 @@ class Engine:
             self.lib.call("ds_partial_sum_f64", self._p(stats), stats.shape[0], self._p(sums), c, self._stream(stats))
             sums[2 * c] = float(count)
             reducer.all_reduce_sum_(sums)
-            self.lib.call("ds_bn_stats_from_sums_f32", self._p(sums), 0, self._p(bn.weight.detach()),
-                          self._p(bn.bias.detach()), BN_EPS, BN_MOMENTUM,
-                          self._p(bn.running_mean) if update_running else None,
-                          self._p(bn.running_var) if update_running else None,
-                          self._p(mean), self._p(invstd), self._p(scale), self._p(shift), c, self._stream(stats))
+            self._bn_from_sums(sums, bn, (mean, invstd, scale, shift), update_running)
             return mean, invstd, scale, shift
         self.lib.call("ds_bn_stats_finalize_f32", self._p(stats), stats.shape[0], count,
                       self._p(bn.weight.detach()), self._p(bn.bias.detach()), BN_EPS, BN_MOMENTUM,
@@ -467,12 +468,15 @@ class Engine:
 
     # ------------------------------------------------------------------ cached launch plan (eval)
     def _build_eval_plan(self, x, pw: PackedWeights, folded, precision: str, masked: bool = False,
-                         low_latency: bool = False):
+                         low_latency: bool = False, per_layer: bool = False, taps: Optional[dict] = None):
         """Everything that does not change between two eval forwards of the same shape -- tile plans are
         recomputed inside the library anyway, but the Python side of a launch (shape structs, pointer
         objects, activation buffers, the stream handle lookup) costs more than the launch itself at
         ~100k embeddings/s.  The plan owns the intermediate activations (re-used by the next call on the
-        same stream); input, output and stream are patched into three mutable ctypes slots per call."""
+        same stream); input, output and stream are patched into three mutable ctypes slots per call.
+
+        `per_layer` (forward_eval): one launch per convolution, channels-last throughout -- no fused BasicBlock
+        kernel, no channel-plane layout; `taps` then receives every stage's three activation buffers."""
         B, _, T, F = x.shape
         dev = x.device
         lowp = precision != "f32"
@@ -536,7 +540,7 @@ class Engine:
         # 128-byte line of which every chunk would read a quarter (4x the HBM / L2 traffic, measured).  Nobody else
         # reads that tensor (masked variable-length plans too: the fused block zeroes the rows past an utterance's
         # extent itself).  The split-K small-launch plans keep channels-last.
-        planes = h16 and not low_latency and len(pw.stages) > 1
+        planes = h16 and not low_latency and not per_layer and len(pw.stages) > 1
         for s, sw in enumerate(pw.stages):
             i, c = s + 1, STAGE_CHANNELS[s]
             sc, sh = folded[f"model.bn{i}"]
@@ -553,7 +557,9 @@ class Engine:
             mask_call(a, s, h)
             cin = c
             last_stage = s == len(pw.stages) - 1
-            if h16 and self.lib.raw("ds_conv_block_f16_supported")(B, h, w, c) == 1:
+            if taps is not None:
+                taps[f"stage{i}.a"] = a
+            if h16 and not per_layer and self.lib.raw("ds_conv_block_f16_supported")(B, h, w, c) == 1:
                 # the shallow stages: the whole BasicBlock as one kernel, the intermediate activation in LDS only
                 # (masked batches: the kernel zeroes the rows past each utterance's extent after both layers itself)
                 sc1, sh1 = folded[f"model.layer{i}.0.bn1"]
@@ -577,8 +583,9 @@ class Engine:
             mask_call(y, s, h)
             sc, sh = folded[f"model.layer{i}.0.bn2"]
             a, _, _ = conv_call(self._p(y), sw.l_conv2, sw.l_conv2_bf16, B, h, w, c, c, 3, 1, sc, sh, a, sw.l_conv2_f16,
-                                last=(s == len(pw.stages) - 1),
-                                layout_flags=DS_EPI_OUT_PLANES16 if (planes and i == 1) else 0)
+                                last=last_stage, layout_flags=DS_EPI_OUT_PLANES16 if (planes and i == 1) else 0)
+            if taps is not None:
+                taps[f"stage{i}.b"], taps[f"stage{i}.c"] = y, a
             if s < len(pw.stages) - 1:          # (the masked pool below never reads the last stage's padding rows)
                 mask_call(a, s, h)
         k = w * cin
@@ -626,6 +633,18 @@ class Engine:
         plans.clear()
         return freed
 
+    def _check_eval_args(self, x: torch.Tensor, pw: PackedWeights, precision: str):
+        self._check(x, "input")
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise ValueError("input must be [B,1,T,F] (reference model.py:185, SURVEY F1)")
+        if precision not in PRECISIONS:
+            raise ValueError(f"unknown precision {precision!r}; expected one of {PRECISIONS}")
+        if precision == "f16":
+            if pw.stages[0].l_conv1_f16 is None:
+                raise ValueError("pack_weights(..., with_f16=True) is required for precision 'f16'")
+        elif precision != "f32" and pw.stages[0].l_conv1_bf16 is None:
+            raise ValueError("pack_weights(..., with_bf16=True) is required for the bf16 precisions")
+
     def forward_eval_planned(self, x: torch.Tensor, pw: PackedWeights, folded, precision: str = "f32",
                              lengths: Optional[torch.Tensor] = None, low_latency: bool = False) -> torch.Tensor:
         """forward_eval through a launch plan cached per (shape, weights version, precision, device).
@@ -638,16 +657,7 @@ class Engine:
         `low_latency` (fp16 path): launches too small to fill the GPU split their contraction over several
         workgroups per tile (serving one or a few utterances); results then differ from the one-pass path by the f32
         summation order."""
-        self._check(x, "input")
-        if x.dim() != 4 or x.shape[1] != 1:
-            raise ValueError("input must be [B,1,T,F] (reference model.py:185, SURVEY F1)")
-        if precision not in PRECISIONS:
-            raise ValueError(f"unknown precision {precision!r}; expected one of {PRECISIONS}")
-        if precision == "f16":
-            if pw.stages[0].l_conv1_f16 is None:
-                raise ValueError("pack_weights(..., with_f16=True) is required for precision 'f16'")
-        elif precision != "f32" and pw.stages[0].l_conv1_bf16 is None:
-            raise ValueError("pack_weights(..., with_bf16=True) is required for the bf16 precisions")
+        self._check_eval_args(x, pw, precision)
         # the plan owns its intermediate activations: forwards in flight on different streams need their own
         stream_id = torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else 0
         key = (tuple(x.shape), precision, id(pw), id(folded), x.device, stream_id, lengths is not None, low_latency)
@@ -688,15 +698,20 @@ class Engine:
                 host = host.pin_memory()
             plan["lens"].copy_(host, non_blocking=True)
             plan["lens_host"] = host                    # keeps the pinned staging copy alive until the next call
-        e = torch.empty((x.shape[0], plan["n_out"]), dtype=torch.float32, device=x.device)
-        plan["x"].value, plan["e"].value = x.data_ptr(), e.data_ptr()
-        plan["st"].value = torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else None
         prof = self.profile if (self.profile is not None and x.is_cuda) else None
         if prof is not None and self.profile_every > 1:
             turn = self._profile_calls.get(precision, 0)
             self._profile_calls[precision] = turn + 1
             if turn % self.profile_every:
                 prof = None
+        return self._run_eval_plan(plan, x, precision, prof, self.self_timed_launches)
+
+    def _run_eval_plan(self, plan, x: torch.Tensor, precision: str, prof: Optional[list], self_timed: bool) -> torch.Tensor:
+        """Enqueue a plan's launches for input `x` on the current stream; `prof`: the list the labelled (convolution)
+        launches append their timing entries to, or None."""
+        e = torch.empty((x.shape[0], plan["n_out"]), dtype=torch.float32, device=x.device)
+        plan["x"].value, plan["e"].value = x.data_ptr(), e.data_ptr()
+        plan["st"].value = torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else None
         roctx = _Range.enabled and x.is_cuda
         if roctx:
             torch.cuda.nvtx.range_push(f"ds.forward_eval[{precision}] B={x.shape[0]} T={x.shape[2]}")
@@ -704,7 +719,7 @@ class Engine:
             if roctx:
                 torch.cuda.nvtx.mark(label or fn.__name__)
             if prof is not None and label is not None:
-                if self.self_timed_launches and fn.__name__ in _SELF_TIMED:    # one MFMA kernel per call: the launch carries its own events
+                if self_timed and fn.__name__ in _SELF_TIMED:    # one MFMA kernel per call: the launch carries its own events
                     ev0, ev1 = LaunchEvent(self.lib), LaunchEvent(self.lib)
                     self.lib.call("ds_launch_timing_arm", ev0.handle, ev1.handle)
                     rc = fn(*args)
@@ -735,58 +750,14 @@ class Engine:
         precision: "f32" exact-f32 MFMA (the parity path); "bf16x3" split-operand bf16 MFMA (f32-class
         accuracy); "f16" fp16 operands and fp16 activations in HBM, f32 accumulate (the throughput path, 3.7e-4
         from the reference); "bf16" plain bf16 operands (3e-3: outside the contract).  conv1 runs its
-        split-operand bf16 kernel in all low-precision modes; fc and the tail are f32 in all modes."""
-        if precision not in PRECISIONS:
-            raise ValueError(f"unknown precision {precision!r}; expected one of {PRECISIONS}")
-        lowp = precision != "f32"
-        x3 = precision == "bf16x3"
-        h16 = precision == "f16"
-        if h16:
-            if pw.stages[0].l_conv1_f16 is None:
-                raise ValueError("pack_weights(..., with_f16=True) is required for precision 'f16'")
-        elif lowp and pw.stages[0].l_conv1_bf16 is None:
-            raise ValueError("pack_weights(..., with_bf16=True) is required for the bf16 precisions")
-        self._check(x, "input")
-        B, one, T, F = x.shape
-        if one != 1:
-            raise ValueError("input must be [B,1,T,F] (reference model.py:185, SURVEY F1)")
-        h, w, cin = T, F, 1
-        a = x
-        AC = DS_EPI_AFFINE | DS_EPI_CLIP
-        for s, sw in enumerate(pw.stages):
-            i, c = s + 1, STAGE_CHANNELS[s]
-            sc, sh = folded[f"model.bn{i}"]
-            if i == 1:
-                a, _ = self.conv1(a, sw.conv, B, h, w, sc, sh, AC | (DS_EPI_OUT_F16 if h16 else 0), lowp=lowp)
-            elif h16:
-                a = self.conv_f16(a, sw.conv_f16, B, h, w, cin, c, 5, 2, sc, sh, None, AC)
-            elif lowp:
-                a = self.conv_bf16(a, sw.conv_bf16, x3, B, h, w, cin, c, 5, 2, sc, sh, None, AC)
-            else:
-                a, _ = self.conv(a, sw.conv, B, h, w, cin, c, 5, 2, sc, sh, None, AC)
-            h, w, cin = conv_out(h, 5, 2), conv_out(w, 5, 2), c
-            if taps is not None:
-                taps[f"stage{i}.a"] = a
-            sc, sh = folded[f"model.layer{i}.0.bn1"]
-            if h16:
-                y = self.conv_f16(a, sw.l_conv1_f16, B, h, w, c, c, 3, 1, sc, sh, None, AC)
-            elif lowp:
-                y = self.conv_bf16(a, sw.l_conv1_bf16, x3, B, h, w, c, c, 3, 1, sc, sh, None, AC)
-            else:
-                y, _ = self.conv(a, sw.l_conv1, B, h, w, c, c, 3, 1, sc, sh, None, AC)
-            if taps is not None:
-                taps[f"stage{i}.b"] = y
-            sc, sh = folded[f"model.layer{i}.0.bn2"]
-            if h16:         # the last layer hands f32 to the (f32) pooling / projection tail
-                last = DS_EPI_OUT_F32 if s == len(pw.stages) - 1 else 0
-                a = self.conv_f16(y, sw.l_conv2_f16, B, h, w, c, c, 3, 1, sc, sh, a, AC | DS_EPI_RESIDUAL | last)
-            elif lowp:
-                a = self.conv_bf16(y, sw.l_conv2_bf16, x3, B, h, w, c, c, 3, 1, sc, sh, a, AC | DS_EPI_RESIDUAL)
-            else:
-                a, _ = self.conv(y, sw.l_conv2, B, h, w, c, c, 3, 1, sc, sh, a, AC | DS_EPI_RESIDUAL)
-            if taps is not None:
-                taps[f"stage{i}.c"] = a
-        return self.tail(a, pw)
+        split-operand bf16 kernel in all low-precision modes; fc and the tail are f32 in all modes.
+
+        One launch per layer through an uncached per-layer plan (fresh activation buffers: `taps` receives
+        "stage{i}.a|b|c"); every convolution launch is profiled (no `profile_every` turn is taken)."""
+        self._check_eval_args(x, pw, precision)
+        plan = self._build_eval_plan(x, pw, folded, precision, per_layer=True, taps=taps)
+        prof = self.profile if (self.profile is not None and x.is_cuda) else None
+        return self._run_eval_plan(plan, x, precision, prof, self_timed=False)
 
     def forward_train(self, x: torch.Tensor, pw: PackedWeights, bns: Dict[str, BNParams],
                       save: bool = True, reducer=None, precision: str = "f32") -> Tuple[torch.Tensor, Optional[SavedForward]]:
@@ -797,48 +768,81 @@ class Engine:
         B, one, T, F = x.shape
         if one != 1:
             raise ValueError("input must be [B,1,T,F]")
-        saved = SavedForward(x=x) if save else None
         if precision not in ("f32", "bf16x3"):
             raise ValueError("training runs in f32 or bf16x3 (the plain-bf16 speed mode is eval-only)")
         x3 = precision == "bf16x3"
         if x3 and pw.stages[0].l_conv1_bf16 is None:
             raise ValueError("pack_weights(..., with_bf16=True) is required for bf16x3")
 
-        def conv_s(src, w_f32, w_b, Bc, hh, ww, ci, co, ks, stride):
-            if x3:
-                return self.conv_bf16(src, w_b, True, Bc, hh, ww, ci, co, ks, stride, want_stats=True)
-            return self.conv(src, w_f32, Bc, hh, ww, ci, co, ks, stride, want_stats=True)
+        def layer(src, sw, conv, name, geom, residual, last):
+            z, st = self._conv_train(src, sw, conv, B, geom, x3)
+            stats = self.bn_finalize(st, z.numel() // z.shape[-1], bns[name], reducer=reducer)
+            return z, self.bn_apply(z, stats[2], stats[3], residual, _clip_flags(residual)), stats
 
-        h, w, cin = T, F, 1
+        a, saved = self._train_walk(x, pw, save, layer)
+        return self.tail(a, pw, saved), saved
+
+    # ------------------------------------------------------------------ the train-mode layer walk
+    def _train_walk(self, x: torch.Tensor, pw: PackedWeights, save: bool, layer):
+        """The layer sequence of every train-mode forward (reference model.py:185-208): per stage the 5x5 stride-2
+        convolution (stage 1: the Cin = 1 conv1), then the BasicBlock's two 3x3 convolutions, each followed by
+        BatchNorm(train) and the clip, the second adding the block's input.  This loop owns the order, the dims and the
+        `saved` bookkeeping; `layer(src, sw, conv, bn_name, geom, residual, last)` is the schedule's routine for one such
+        layer (`conv`: the StageWeights attribute stem; `geom`: (h, w, cin, cout, ks, stride) of its input; `last`: the
+        network's last layer) and returns (raw output, activation, statistics).  Returns (last activation, saved)."""
+        saved = SavedForward(x=x) if save else None
+        h, w, cin = x.shape[2], x.shape[3], 1
         a = x
+
+        def step(src, sw, conv, name, tap, geom, residual=None, last=False):
+            z, out, stats = layer(src, sw, conv, name, geom, residual, last)
+            if save:
+                saved.raws[name], saved.stats[name], saved.acts[tap] = z, stats, out
+            return out
+
         for s, sw in enumerate(pw.stages):
             i, c = s + 1, STAGE_CHANNELS[s]
-            if i == 1:
-                z, st = self.conv1(a, sw.conv, B, h, w, want_stats=True, lowp=x3)
-            else:
-                z, st = conv_s(a, sw.conv, sw.conv_bf16, B, h, w, cin, c, 5, 2)
+            a = step(a, sw, "conv", f"model.bn{i}", f"stage{i}.a", (h, w, cin, c, 5, 2))
             h, w, cin = conv_out(h, 5, 2), conv_out(w, 5, 2), c
-            count = B * h * w
-            name = f"model.bn{i}"
-            mean, invstd, sc, sh = self.bn_finalize(st, count, bns[name], reducer=reducer)
-            a = self.bn_apply(z, sc, sh, None, DS_EPI_CLIP)
+            y = step(a, sw, "l_conv1", f"model.layer{i}.0.bn1", f"stage{i}.b", (h, w, c, c, 3, 1))
+            a = step(y, sw, "l_conv2", f"model.layer{i}.0.bn2", f"stage{i}.c", (h, w, c, c, 3, 1), a,
+                     s == len(pw.stages) - 1)
             if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.a"] = z, (mean, invstd, sc, sh), a
-            name = f"model.layer{i}.0.bn1"
-            z, st = conv_s(a, sw.l_conv1, sw.l_conv1_bf16, B, h, w, c, c, 3, 1)
-            mean, invstd, sc, sh = self.bn_finalize(st, count, bns[name], reducer=reducer)
-            y = self.bn_apply(z, sc, sh, None, DS_EPI_CLIP)
-            if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.b"] = z, (mean, invstd, sc, sh), y
-            name = f"model.layer{i}.0.bn2"
-            z, st = conv_s(y, sw.l_conv2, sw.l_conv2_bf16, B, h, w, c, c, 3, 1)
-            mean, invstd, sc, sh = self.bn_finalize(st, count, bns[name], reducer=reducer)
-            a = self.bn_apply(z, sc, sh, a, DS_EPI_CLIP | DS_EPI_RESIDUAL)
-            if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.c"] = z, (mean, invstd, sc, sh), a
                 saved.dims.append((h, w))
-        e = self.tail(a, pw, saved)
-        return e, saved
+        return a, saved
+
+    def _conv_train(self, src, sw: StageWeights, conv: str, B: int, geom, x3: bool, out=None):
+        """Raw output + per-tile partial statistics of one train-mode convolution of a batch of B: conv1 (Cin = 1, the
+        exact VALU kernel or its split-operand twin), else the 5x5 / 3x3 layer `sw.<conv>` in f32 or `sw.<conv>_bf16`."""
+        h, w, cin, cout, ks, stride = geom
+        if cin == 1:
+            return self.conv1(src, sw.conv, B, h, w, want_stats=True, lowp=x3, out=out)
+        if x3:
+            return self.conv_bf16(src, getattr(sw, conv + "_bf16"), True, B, *geom, want_stats=True, out=out)
+        return self.conv(src, getattr(sw, conv), B, *geom, want_stats=True, out=out)
+
+    def _bn_from_sums(self, sums: torch.Tensor, bn: BNParams, out, update_running: bool = True):
+        """(mean, invstd, scale, shift) -> `out` from one [2C + 1] float64 sum row (data parallelism: the global batch's)"""
+        self.lib.call("ds_bn_stats_from_sums_f32", self._p(sums), 0, self._p(bn.weight.detach()), self._p(bn.bias.detach()),
+                      BN_EPS, BN_MOMENTUM, self._p(bn.running_mean) if update_running else None,
+                      self._p(bn.running_var) if update_running else None, *(self._p(t) for t in out), bn.weight.numel(),
+                      self._stream(sums))
+
+    def _members(self, xs: List[torch.Tensor]):
+        """G equally shaped [B,1,T,F] members -> (one [G*B,1,T,F] batch, B).  Members that already are consecutive
+        slices of one buffer (a resident batch split into a / p / n) are used in place; otherwise they are concatenated."""
+        for x in xs:
+            self._check(x, "input")
+            if x.shape != xs[0].shape or x.dim() != 4 or x.shape[1] != 1:
+                raise ValueError("members must be equally shaped [B,1,T,F] batches")
+        G, (Bm, _, T, F) = len(xs), xs[0].shape
+        nbytes = xs[0].numel() * xs[0].element_size()
+        if G == 1:
+            return xs[0], Bm
+        if all(x.is_contiguous() and x.data_ptr() == xs[0].data_ptr() + g * nbytes
+               and x.untyped_storage().data_ptr() == xs[0].untyped_storage().data_ptr() for g, x in enumerate(xs)):
+            return torch.as_strided(xs[0], (G * Bm, 1, T, F), xs[0].stride()), Bm
+        return torch.cat(xs), Bm
 
     # ------------------------------------------------------------------ grouped train-mode forward
     def _group_aligned(self, shp: ConvShape, members: int, x3: bool) -> bool:
@@ -876,20 +880,8 @@ class Engine:
         if precision not in ("f32", "bf16x3"):
             raise ValueError("training runs in f32 or bf16x3")
         G = len(xs)
-        for x in xs:
-            self._check(x, "input")
-            if x.shape != xs[0].shape or x.dim() != 4 or x.shape[1] != 1:
-                raise ValueError("members must be equally shaped [B,1,T,F] batches")
-        Bm, _, T, F = xs[0].shape
+        x, Bm = self._members(xs)
         B = G * Bm
-        # members that already are consecutive slices of one buffer (a resident batch split into a / p / n) are used
-        # in place; otherwise they are concatenated
-        nbytes = xs[0].numel() * xs[0].element_size()
-        if all(x.is_contiguous() and x.data_ptr() == xs[0].data_ptr() + g * nbytes
-               and x.untyped_storage().data_ptr() == xs[0].untyped_storage().data_ptr() for g, x in enumerate(xs)):
-            x = torch.as_strided(xs[0], (B, 1, T, F), xs[0].stride())
-        else:
-            x = torch.cat(xs)
         x3 = precision == "bf16x3"
         if x3 and pw.stages[0].l_conv1_bf16 is None:
             raise ValueError("pack_weights(..., with_bf16=True) is required for bf16x3")
@@ -897,104 +889,59 @@ class Engine:
         dp = reducer is not None and reducer.active
         if self.MEMBER_STREAMS and save and x.is_cuda and G > 1 and (not dp or self.MEMBER_STREAMS_DP):
             return self._forward_train_group_streams(x, G, pw, bns, save, x3, reducer if dp else None)
-        saved = SavedForward(x=x) if save else None
         dev = x.device
 
         def member(t, g):
             return t[g * Bm:(g + 1) * Bm]
 
-        def conv_g(src, w_f32, w_b, hh, ww, ci, co, ks, stride):
-            """raw conv output [B,ho,wo,co] + per-member partial statistics"""
-            shp = ConvShape(B, hh, ww, ci, co, ks, stride)
-            if G == 1 or self._group_aligned(shp, G, x3):
-                if x3:
-                    z, st = self.conv_bf16(src, w_b, True, B, hh, ww, ci, co, ks, stride, want_stats=True)
-                else:
-                    z, st = self.conv(src, w_f32, B, hh, ww, ci, co, ks, stride, want_stats=True)
-                rows = st.shape[0] // G
-                return z, [st[g * rows:(g + 1) * rows] for g in range(G)]
-            ho, wo = conv_out(hh, ks, stride), conv_out(ww, ks, stride)
-            z = torch.empty((B, ho, wo, co), dtype=torch.float32, device=dev)
-            sts = []
-            for g in range(G):
-                if x3:
-                    zg, st = self.conv_bf16(member(src, g), w_b, True, Bm, hh, ww, ci, co, ks, stride, want_stats=True)
-                else:
-                    zg, st = self.conv(member(src, g), w_f32, Bm, hh, ww, ci, co, ks, stride, want_stats=True)
-                member(z, g).copy_(zg)
-                sts.append(st)
-            return z, sts
-
-        def bn_g(z, sts, name, count, residual, flags):
-            """per-member statistics -> normalised (+ residual) + clipped activations of the whole batch"""
-            bn = bns[name]
-            c = bn.weight.numel()
-            per = []
-            if reducer is not None and reducer.active:
-                sums = torch.empty((G, 2 * c + 1), dtype=torch.float64, device=dev)
-                rows = sts[0].shape[0]
-                if all(st_.shape[0] == rows and st_.data_ptr() == sts[0].data_ptr() + g * rows * c * 8
-                       for g, st_ in enumerate(sts)):
-                    # the members' partial rows are consecutive slices of one launch's statistics: one kernel
-                    self.lib.call("ds_partial_sum_f64_group", self._p(sts[0]), rows, self._p(sums), count, c, G,
-                                  self._stream(z))
-                else:
-                    for g in range(G):
-                        self.lib.call("ds_partial_sum_f64", self._p(sts[g]), sts[g].shape[0], self._p(sums[g]), c,
-                                      self._stream(z))
-                    sums[:, 2 * c] = float(count)
-                reducer.all_reduce_sum_(sums)                     # all members of this layer in ONE collective
-                # mean / invstd / scale / shift as rows of one [G][C] table each (as below): the backward pass stays grouped
-                mean_all, invstd_all, sc_all, sh_all = torch.empty((4, G, c), dtype=torch.float32, device=dev).unbind(0)
-                for g in range(G):                                # running statistics update in call order
-                    mean, invstd, sc, sh = mean_all[g], invstd_all[g], sc_all[g], sh_all[g]
-                    self.lib.call("ds_bn_stats_from_sums_f32", self._p(sums[g]), 0, self._p(bn.weight.detach()),
-                                  self._p(bn.bias.detach()), BN_EPS, BN_MOMENTUM, self._p(bn.running_mean),
-                                  self._p(bn.running_var), self._p(mean), self._p(invstd), self._p(sc), self._p(sh), c,
-                                  self._stream(z))
-                    per.append((mean, invstd, sc, sh))
-            else:
-                # the members' mean / invstd (and scale / shift) as rows of one [G][C] tensor each: the backward pass then
-                # runs every BatchNorm layer's reductions for all members in one launch (backward._bn_bwd_group), or
-                # inside the data-gradient kernel above it (backward._dgrad_bn_bwd)
-                mean_all, invstd_all, sc_all, sh_all = torch.empty((4, G, c), dtype=torch.float32, device=dev).unbind(0)
-                for g in range(G):                                # running statistics update in call order
-                    per.append(self.bn_finalize(sts[g], count, bn, out=(mean_all[g], invstd_all[g], sc_all[g], sh_all[g])))
-            a = torch.empty_like(z)
-            n_pix = member(z, 0).numel() // c
-            for g in range(G):
-                self.lib.call("ds_bn_apply_f32", self._p(member(z, g)), self._p(per[g][2]), self._p(per[g][3]),
-                              self._p(member(residual, g)) if residual is not None else None, self._p(member(a, g)),
-                              n_pix, c, flags, self._stream(z))
-            return a, list(per)
-
-        h, w, cin = T, F, 1
-        a = x
-        for s, sw in enumerate(pw.stages):
-            i, c = s + 1, STAGE_CHANNELS[s]
-            if i == 1:
-                z, st = self.conv1(a, sw.conv, B, h, w, want_stats=True, lowp=x3)     # its tiles never span images
+        def layer(src, sw, conv, name, geom, residual, last):
+            h, w, cin, cout, ks, stride = geom
+            # raw output [B,ho,wo,cout] + per-member partial statistics: one launch over all members wherever its tiles
+            # stay inside one member (conv1's never span images), otherwise one per member into slices of one buffer
+            if cin == 1 or G == 1 or self._group_aligned(ConvShape(B, *geom), G, x3):
+                z, st = self._conv_train(src, sw, conv, B, geom, x3)
                 rows = st.shape[0] // G
                 sts = [st[g * rows:(g + 1) * rows] for g in range(G)]
             else:
-                z, sts = conv_g(a, sw.conv, sw.conv_bf16, h, w, cin, c, 5, 2)
-            h, w, cin = conv_out(h, 5, 2), conv_out(w, 5, 2), c
-            count = Bm * h * w
-            name = f"model.bn{i}"
-            a, stt = bn_g(z, sts, name, count, None, DS_EPI_CLIP)
-            if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.a"] = z, stt, a
-            name = f"model.layer{i}.0.bn1"
-            z, sts = conv_g(a, sw.l_conv1, sw.l_conv1_bf16, h, w, c, c, 3, 1)
-            y, stt = bn_g(z, sts, name, count, None, DS_EPI_CLIP)
-            if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.b"] = z, stt, y
-            name = f"model.layer{i}.0.bn2"
-            z, sts = conv_g(y, sw.l_conv2, sw.l_conv2_bf16, h, w, c, c, 3, 1)
-            a, stt = bn_g(z, sts, name, count, a, DS_EPI_CLIP | DS_EPI_RESIDUAL)
-            if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.c"] = z, stt, a
-                saved.dims.append((h, w))
+                z = torch.empty((B, conv_out(h, ks, stride), conv_out(w, ks, stride), cout), dtype=torch.float32, device=dev)
+                sts = []
+                for g in range(G):
+                    zg, st = self._conv_train(member(src, g), sw, conv, Bm, geom, x3)
+                    member(z, g).copy_(zg)
+                    sts.append(st)
+            # per-member statistics -> normalised (+ residual) + clipped activations of the whole batch
+            bn = bns[name]
+            count = z.numel() // cout // G
+            if dp:
+                sums = torch.empty((G, 2 * cout + 1), dtype=torch.float64, device=dev)
+                rows = sts[0].shape[0]
+                if all(st_.shape[0] == rows and st_.data_ptr() == sts[0].data_ptr() + g * rows * cout * 8
+                       for g, st_ in enumerate(sts)):
+                    # the members' partial rows are consecutive slices of one launch's statistics: one kernel
+                    self.lib.call("ds_partial_sum_f64_group", self._p(sts[0]), rows, self._p(sums), count, cout, G,
+                                  self._stream(z))
+                else:
+                    for g in range(G):
+                        self.lib.call("ds_partial_sum_f64", self._p(sts[g]), sts[g].shape[0], self._p(sums[g]), cout,
+                                      self._stream(z))
+                    sums[:, 2 * cout] = float(count)
+                reducer.all_reduce_sum_(sums)                     # all members of this layer in ONE collective
+            # the members' mean / invstd (and scale / shift) as rows of one [G][C] tensor each: the backward pass then
+            # runs every BatchNorm layer's reductions for all members in one launch (backward._bn_bwd_group), or
+            # inside the data-gradient kernel above it (backward._dgrad_bn_bwd)
+            per = list(zip(*torch.empty((4, G, cout), dtype=torch.float32, device=dev)))
+            for g in range(G):                                    # running statistics update in call order
+                if dp:
+                    self._bn_from_sums(sums[g], bn, per[g])
+                else:
+                    self.bn_finalize(sts[g], count, bn, out=per[g])
+            a = torch.empty_like(z)
+            for g in range(G):
+                self.bn_apply(member(z, g), per[g][2], per[g][3], member(residual, g) if residual is not None else None,
+                              _clip_flags(residual), out=member(a, g))
+            return z, a, per
+
+        a, saved = self._train_walk(x, pw, save, layer)
         e = self.tail(a, pw, saved)
         return [member(e, g) for g in range(G)], saved
 
@@ -1029,7 +976,6 @@ class Engine:
         if key not in Engine._member_streams:
             Engine._member_streams[key] = [torch.cuda.Stream(device=dev) for _ in range(G)]
         streams = Engine._member_streams[key]
-        saved = SavedForward(x=x) if save else None
         keep = []                  # data-parallel: the layers' sum tables, alive until the streams have joined
         for st in streams:
             st.wait_stream(cur)
@@ -1037,40 +983,47 @@ class Engine:
         def member(t, g):
             return t[g * Bm:(g + 1) * Bm]
 
-        def layer(src, name, kind, sw_f32, sw_b, hh, ww, ci, co, residual):
-            """one convolution + BatchNorm(train) + clip layer of all members; returns (z, a, stats list)"""
-            ks, stride = (5, 2) if kind != "3x3" else (3, 1)
-            ho, wo = conv_out(hh, ks, stride), conv_out(ww, ks, stride)
-            z = torch.empty((B, ho, wo, co), dtype=torch.float32, device=dev)
+        def layer(src, sw, conv, name, geom, residual, last):
+            """one convolution + BatchNorm(train) + clip layer of all members"""
+            h, w, cin, cout, ks, stride = geom
+            z = torch.empty((B, conv_out(h, ks, stride), conv_out(w, ks, stride), cout), dtype=torch.float32, device=dev)
             a = torch.empty_like(z)
-            tables = torch.empty((4, G, co), dtype=torch.float32, device=dev)
-            mean_all, invstd_all, sc_all, sh_all = tables.unbind(0)
+            per = list(zip(*torch.empty((4, G, cout), dtype=torch.float32, device=dev)))
             bn = bns[name]
-            count = Bm * ho * wo
-            flags = DS_EPI_CLIP | (DS_EPI_RESIDUAL if residual is not None else 0)
+            count = z.numel() // cout // G
             prev_done = None
-            per = []
             if reducer is not None:
-                # data parallel: ONE all-reduce carries the three members' sums of this layer -- the members' streams
-                # meet there (member 0's stream issues it) and part again for their normalise + clip passes
-                sums = torch.empty((G, 2 * co + 1), dtype=torch.float64, device=dev)
+                # data parallel: ONE all-reduce carries the members' sums of this layer -- the members' streams meet
+                # there (member 0's stream issues it) and part again for their normalise + clip passes
+                sums = torch.empty((G, 2 * cout + 1), dtype=torch.float64, device=dev)
                 keep.append(sums)
                 ready = []
-                for g in range(G):
-                    with torch.cuda.stream(streams[g]):
-                        if kind == "c1":
-                            _, stp = self.conv1(member(src, g), sw_f32, Bm, hh, ww, want_stats=True, lowp=x3, out=member(z, g))
-                        elif x3:
-                            _, stp = self.conv_bf16(member(src, g), sw_b, True, Bm, hh, ww, ci, co, ks, stride,
-                                                    want_stats=True, out=member(z, g))
-                        else:
-                            _, stp = self.conv(member(src, g), sw_f32, Bm, hh, ww, ci, co, ks, stride, want_stats=True,
-                                               out=member(z, g))
-                        self.lib.call("ds_partial_sum_f64_group", self._p(stp), stp.shape[0], self._p(sums[g]), count, co,
-                                      1, self._stream(z))
-                        ev = torch.cuda.Event()
-                        ev.record(streams[g])
-                        ready.append(ev)
+            sts = []
+
+            def finish(g):
+                nonlocal prev_done
+                if prev_done is not None:
+                    streams[g].wait_event(prev_done)              # running statistics: a, then p, then n
+                if reducer is not None:
+                    self._bn_from_sums(sums[g], bn, per[g])
+                else:
+                    self.bn_finalize(sts[g], count, bn, out=per[g])
+                prev_done = torch.cuda.Event()
+                prev_done.record(streams[g])
+                self.bn_apply(member(z, g), per[g][2], per[g][3], member(residual, g) if residual is not None else None,
+                              _clip_flags(residual), out=member(a, g))
+
+            for g in range(G):
+                with torch.cuda.stream(streams[g]):
+                    sts.append(self._conv_train(member(src, g), sw, conv, Bm, geom, x3, out=member(z, g))[1])
+                    if reducer is None:
+                        finish(g)
+                        continue
+                    self.lib.call("ds_partial_sum_f64_group", self._p(sts[g]), sts[g].shape[0], self._p(sums[g]), count,
+                                  cout, 1, self._stream(z))
+                    ready.append(torch.cuda.Event())
+                    ready[g].record(streams[g])
+            if reducer is not None:
                 with torch.cuda.stream(streams[0]):
                     for ev in ready[1:]:
                         streams[0].wait_event(ev)
@@ -1080,57 +1033,10 @@ class Engine:
                 for g in range(G):
                     with torch.cuda.stream(streams[g]):
                         streams[g].wait_event(reduced)
-                        if prev_done is not None:
-                            streams[g].wait_event(prev_done)      # running statistics: a, then p, then n
-                        self.lib.call("ds_bn_stats_from_sums_f32", self._p(sums[g]), 0, self._p(bn.weight.detach()),
-                                      self._p(bn.bias.detach()), BN_EPS, BN_MOMENTUM, self._p(bn.running_mean),
-                                      self._p(bn.running_var), self._p(mean_all[g]), self._p(invstd_all[g]),
-                                      self._p(sc_all[g]), self._p(sh_all[g]), co, self._stream(z))
-                        prev_done = torch.cuda.Event()
-                        prev_done.record(streams[g])
-                        self.bn_apply(member(z, g), sc_all[g], sh_all[g],
-                                      member(residual, g) if residual is not None else None, flags, out=member(a, g))
-                        per.append((mean_all[g], invstd_all[g], sc_all[g], sh_all[g]))
-                return z, a, per, ho, wo
-            for g in range(G):
-                with torch.cuda.stream(streams[g]):
-                    if kind == "c1":
-                        _, stp = self.conv1(member(src, g), sw_f32, Bm, hh, ww, want_stats=True, lowp=x3, out=member(z, g))
-                    elif x3:
-                        _, stp = self.conv_bf16(member(src, g), sw_b, True, Bm, hh, ww, ci, co, ks, stride,
-                                                want_stats=True, out=member(z, g))
-                    else:
-                        _, stp = self.conv(member(src, g), sw_f32, Bm, hh, ww, ci, co, ks, stride, want_stats=True,
-                                           out=member(z, g))
-                    if prev_done is not None:
-                        streams[g].wait_event(prev_done)          # running statistics: a, then p, then n
-                    out = (mean_all[g], invstd_all[g], sc_all[g], sh_all[g])
-                    self.bn_finalize(stp, count, bn, out=out)
-                    prev_done = torch.cuda.Event()
-                    prev_done.record(streams[g])
-                    self.bn_apply(member(z, g), sc_all[g], sh_all[g], member(residual, g) if residual is not None else None,
-                                  flags, out=member(a, g))
-                    per.append(out)
-            return z, a, per, ho, wo
+                        finish(g)
+            return z, a, per
 
-        h, w, cin = T, F, 1
-        a = x
-        for s_, sw in enumerate(pw.stages):
-            i, c = s_ + 1, STAGE_CHANNELS[s_]
-            name = f"model.bn{i}"
-            z, a, stt, h, w = layer(a, name, "c1" if i == 1 else "5x5", sw.conv, sw.conv_bf16, h, w, cin, c, None)
-            cin = c
-            if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.a"] = z, stt, a
-            name = f"model.layer{i}.0.bn1"
-            z, y, stt, _, _ = layer(a, name, "3x3", sw.l_conv1, sw.l_conv1_bf16, h, w, c, c, None)
-            if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.b"] = z, stt, y
-            name = f"model.layer{i}.0.bn2"
-            z, a, stt, _, _ = layer(y, name, "3x3", sw.l_conv2, sw.l_conv2_bf16, h, w, c, c, a)
-            if save:
-                saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.c"] = z, stt, a
-                saved.dims.append((h, w))
+        a, saved = self._train_walk(x, pw, save, layer)
         for st in streams:
             cur.wait_stream(st)
         e = self.tail(a, pw, saved)

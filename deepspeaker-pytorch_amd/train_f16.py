@@ -30,8 +30,9 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ._native import ConvShape, DS_EPI_CLIP, DS_EPI_OUT_F16, DS_EPI_OUT_F32, DS_EPI_RESIDUAL
-from .engine import ALPHA, BN_EPS, BN_MOMENTUM, L2_EPS, STAGE_CHANNELS, BNParams, Engine, PackedWeights, SavedForward, conv_out
+from ._native import ConvShape, DS_EPI_OUT_F16, DS_EPI_OUT_F32
+from .engine import (ALPHA, BN_EPS, BN_MOMENTUM, L2_EPS, STAGE_CHANNELS, BNParams, Engine, PackedWeights, SavedForward,
+                     _clip_flags)
 
 DEFAULT_LOSS_SCALE = 1024.0
 
@@ -85,52 +86,21 @@ def forward_train_group_f16(eng: Engine, xs: List[torch.Tensor], pw: PackedWeigh
     float64 all-reduce per BatchNorm layer carrying all members' sums.  Returns ([embeddings per member],
     SavedForward with fp16 `raws` / `acts` -- the last stage's output is f32 -- and `stats[name]` = the [4][G][C] tables)."""
     G = len(xs)
-    for x in xs:
-        eng._check(x, "input")
-        if x.shape != xs[0].shape or x.dim() != 4 or x.shape[1] != 1:
-            raise ValueError("members must be equally shaped [B,1,T,F] batches")
+    x, Bm = eng._members(xs)
     if pw.stages[0].l_conv1_f16 is None:
         raise ValueError("pack_weights(..., with_f16=True) is required for the fp16 training step")
-    Bm, _, T, F = xs[0].shape
     B = G * Bm
-    nbytes = xs[0].numel() * xs[0].element_size()
-    if G == 1:
-        x = xs[0]
-    elif all(t.is_contiguous() and t.data_ptr() == xs[0].data_ptr() + g * nbytes
-             and t.untyped_storage().data_ptr() == xs[0].untyped_storage().data_ptr() for g, t in enumerate(xs)):
-        x = torch.as_strided(xs[0], (B, 1, T, F), xs[0].stride())
-    else:
-        x = torch.cat(xs)
-    saved = SavedForward(x=x) if save else None
-    n_stages = len(pw.stages)
-    h, w, cin = T, F, 1
-    a = x
-    for s, sw in enumerate(pw.stages):
-        i, c = s + 1, STAGE_CHANNELS[s]
-        last = s == n_stages - 1
-        if i == 1:      # Cin = 1: the split-operand kernel of the eval path, raw fp16 output
-            z, _ = eng.conv1(a, sw.conv, B, h, w, flags=DS_EPI_OUT_F16, lowp=True)
+
+    def layer(src, sw, conv, name, geom, residual, last):
+        h, w, cin = geom[:3]
+        if cin == 1:        # the split-operand kernel of the eval path, raw fp16 output
+            z, _ = eng.conv1(src, sw.conv, B, h, w, flags=DS_EPI_OUT_F16, lowp=True)
         else:
-            z = eng.conv_f16(a, sw.conv_f16, B, h, w, cin, c, 5, 2)
-        h, w, cin = conv_out(h, 5, 2), conv_out(w, 5, 2), c
-        name = f"model.bn{i}"
+            z = eng.conv_f16(src, getattr(sw, conv + "_f16"), B, *geom)
         tb = _bn_stats(eng, z, bns[name], G, reducer=reducer)
-        a = _bn_apply(eng, z, tb, None, G, DS_EPI_CLIP)
-        if save:
-            saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.a"] = z, tb, a
-        name = f"model.layer{i}.0.bn1"
-        z = eng.conv_f16(a, sw.l_conv1_f16, B, h, w, c, c, 3, 1)
-        tb = _bn_stats(eng, z, bns[name], G, reducer=reducer)
-        y = _bn_apply(eng, z, tb, None, G, DS_EPI_CLIP)
-        if save:
-            saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.b"] = z, tb, y
-        name = f"model.layer{i}.0.bn2"
-        z = eng.conv_f16(y, sw.l_conv2_f16, B, h, w, c, c, 3, 1)
-        tb = _bn_stats(eng, z, bns[name], G, reducer=reducer)
-        a = _bn_apply(eng, z, tb, a, G, DS_EPI_CLIP | DS_EPI_RESIDUAL | (DS_EPI_OUT_F32 if last else 0))
-        if save:
-            saved.raws[name], saved.stats[name], saved.acts[f"stage{i}.c"] = z, tb, a
-            saved.dims.append((h, w))
+        return z, _bn_apply(eng, z, tb, residual, G, _clip_flags(residual) | (DS_EPI_OUT_F32 if last else 0)), tb
+
+    a, saved = eng._train_walk(x, pw, save, layer)
     e = eng.tail(a, pw, saved)
     return [e[g * Bm:(g + 1) * Bm] for g in range(G)], saved
 
