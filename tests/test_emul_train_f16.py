@@ -10,25 +10,35 @@ import torch
 
 import deepspeaker_oracle as O
 from conftest import rel_err
+import train_f16_cases as TC
 from emul_util import aligned, emul_lib, ptr, to_aligned
+from train_f16_cases import r16, rel_l2
 from deepspeaker_pytorch_amd._native import ConvShape, DS_EPI_CLIP, DS_EPI_OUT_F32, DS_EPI_RESIDUAL
-
-
-def r16(a):
-    return np.asarray(a, np.float32).astype(np.float16).astype(np.float32)
 
 
 def nhwc(x, dt=np.float16):
     return to_aligned(np.ascontiguousarray(x.transpose(0, 2, 3, 1)).astype(dt), dt)
 
 
-def rel_l2(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+def flat(x):
+    """NCHW -> the kernels' [pixels, C] view, as train_f16_cases takes it"""
+    return np.ascontiguousarray(x.transpose(0, 2, 3, 1)).reshape(-1, x.shape[1])
 
 
-@pytest.mark.parametrize("G,bm,h,w,c", [(3, 2, 5, 4, 64), (1, 3, 7, 3, 128), (2, 1, 3, 2, 512)])
-def test_bn_stats_apply_f16(G, bm, h, w, c):
+# rows_cls (train_f16_cases.check_rows_class): "mid" = 128 < rows, rows % 128 != 0 -- the fold's `r += 128` loop and its
+# shuffle tree over more than two rows; "cap+0" = the 768-row cap with trailing rows that cover no pixel.  (rows x 16384
+# elements per member whatever C is: the smallest tensors that reach these paths.)
+ROWS_CASES = [(1, 1, 4129, 1, 512, "mid"), (1, 1, 3511, 7, 512, "cap+0")]
+
+
+def _old(*case, extra=()):
+    """a case that predates the path classes: it keeps the test id it has always had"""
+    return pytest.param(*case, *extra, id="-".join(str(v) for v in case))
+
+
+@pytest.mark.parametrize("G,bm,h,w,c,rows_cls", [_old(3, 2, 5, 4, 64, extra=(None,)), _old(1, 3, 7, 3, 128, extra=(None,)),
+                                                 _old(2, 1, 3, 2, 512, extra=(None,))] + ROWS_CASES)
+def test_bn_stats_apply_f16(G, bm, h, w, c, rows_cls):
     lib = emul_lib()
     rs = np.random.RandomState(G * 100 + c)
     z = r16(rs.randn(G * bm, c, h, w) * 3 + 1)
@@ -37,24 +47,25 @@ def test_bn_stats_apply_f16(G, bm, h, w, c):
     rm, rv = (rs.randn(c) * 0.1).astype(np.float32), rs.uniform(0.5, 1.5, c).astype(np.float32)
     n_pix = bm * h * w
     rows = lib.raw("ds_bn_f16_partial_rows")(n_pix, c)
-    partial = aligned((G, rows, c, 2), np.float32)
+    if rows_cls:
+        TC.check_rows_class(rows, n_pix, c, rows_cls)
+    partial = aligned((G, rows, c, 2), np.float32, fill=np.nan)
     tables = aligned((4, G, c), np.float32, fill=np.nan)
     zz = nhwc(z)
     g_, b_, rm_, rv_ = (to_aligned(v.copy()) for v in (gamma, beta, rm, rv))
     lib.call("ds_bn_stats_group_f16", ptr(zz), ptr(partial), n_pix, ptr(g_), ptr(b_), 1e-5, 0.1, ptr(rm_), ptr(rv_),
              ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), ptr(tables[3]), c, G, None)
-    erm, erv = rm.astype(np.float64), rv.astype(np.float64)
-    for m in range(G):                                  # members in call order: three momentum updates
-        zm = z[m * bm:(m + 1) * bm].astype(np.float64)
-        mean, var = zm.mean(axis=(0, 2, 3)), zm.var(axis=(0, 2, 3))
-        np.testing.assert_allclose(tables[0][m], mean, rtol=1e-5, atol=1e-6)
-        np.testing.assert_allclose(tables[1][m], 1 / np.sqrt(var + 1e-5), rtol=1e-5)
-        erm = 0.9 * erm + 0.1 * mean
-        erv = 0.9 * erv + 0.1 * var * n_pix / max(n_pix - 1, 1)
+    mean, var = TC.bn_member_stats(flat(z), G)
+    for m in range(G):
+        np.testing.assert_allclose(tables[0][m], mean[m], rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(tables[1][m], 1 / np.sqrt(var[m] + 1e-5), rtol=1e-5)
+    erm, erv = TC.bn_running_ref(mean, var, n_pix, rm, rv, 0.1)    # members in call order: G momentum updates
     np.testing.assert_allclose(rm_, erm, rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(rv_, erv, rtol=1e-5, atol=1e-6)
-    for flags, out_dt in ((DS_EPI_CLIP, np.float16), (DS_EPI_CLIP | DS_EPI_RESIDUAL, np.float16),
-                          (DS_EPI_CLIP | DS_EPI_RESIDUAL | DS_EPI_OUT_F32, np.float32), (0, np.float16)):
+    variants = ((DS_EPI_CLIP, np.float16), (DS_EPI_CLIP | DS_EPI_RESIDUAL, np.float16),
+                (DS_EPI_CLIP | DS_EPI_RESIDUAL | DS_EPI_OUT_F32, np.float32), (0, np.float16))
+    # (the rows cases are about the reductions: one normalise variant is enough for their large tensors)
+    for flags, out_dt in (variants[1:2] if rows_cls else variants):
         y = aligned((G * bm, h, w, c), out_dt, fill=np.nan)
         rr = nhwc(res)
         lib.call("ds_bn_apply_group_f16", ptr(zz), ptr(tables[2]), ptr(tables[3]), ptr(rr), ptr(y), n_pix, c, G, flags, None)
@@ -70,9 +81,11 @@ def test_bn_stats_apply_f16(G, bm, h, w, c):
         assert np.abs(got - exp).max() <= (1e-5 if out_dt == np.float32 else 1e-2 * max(1.0, np.abs(exp).max()) * 2 ** -3)
 
 
-@pytest.mark.parametrize("G,bm,h,w,c,parity,act32,with_g2", [(3, 2, 6, 4, 64, False, False, True), (2, 1, 5, 7, 128, True, False, False),
-                                                             (1, 2, 4, 4, 256, True, True, True), (3, 1, 3, 3, 64, False, False, False)])
-def test_bn_bwd_group_f16(G, bm, h, w, c, parity, act32, with_g2):
+@pytest.mark.parametrize("G,bm,h,w,c,parity,act32,with_g2,rows_cls",
+                         [_old(3, 2, 6, 4, 64, False, False, True, extra=(None,)), _old(2, 1, 5, 7, 128, True, False, False, extra=(None,)),
+                          _old(1, 2, 4, 4, 256, True, True, True, extra=(None,)), _old(3, 1, 3, 3, 64, False, False, False, extra=(None,)),
+                          (1, 1, 4129, 1, 512, False, False, True, "mid"), (1, 1, 3511, 7, 512, True, False, False, "cap+0")])
+def test_bn_bwd_group_f16(G, bm, h, w, c, parity, act32, with_g2, rows_cls):
     """gy / gz / dgamma / dbeta vs the oracle's BatchNorm + clip backward on the same fp16-rounded inputs, with the
     upstream gradient optionally in the parity-class layout of the stride-2 data gradient (odd map sizes included)"""
     lib = emul_lib()
@@ -88,37 +101,26 @@ def test_bn_bwd_group_f16(G, bm, h, w, c, parity, act32, with_g2):
     invstd_t = np.stack([1 / np.sqrt(z[m * bm:(m + 1) * bm].var(axis=(0, 2, 3)) + 1e-5) for m in range(G)]).astype(np.float32)
     n_pix = bm * h * w
     rows = lib.raw("ds_bn_f16_partial_rows")(n_pix, c)
+    if rows_cls:
+        TC.check_rows_class(rows, n_pix, c, rows_cls)
     if parity:          # [B][ceil(h/2)][ceil(w/2)][2][2][c]; cells past an odd edge hold garbage that must not be read
-        h2, w2 = (h + 1) // 2, (w + 1) // 2
-        g1_dev = aligned((B, h2, w2, 2, 2, c), np.float16, fill=np.nan)
-        g1n = g1.transpose(0, 2, 3, 1)
-        for hh in range(h):
-            for ww in range(w):
-                g1_dev[:, hh >> 1, ww >> 1, hh & 1, ww & 1] = g1n[:, hh, ww]
+        g1_dev = to_aligned(TC.parity_scatter(g1.transpose(0, 2, 3, 1).astype(np.float16), h, w, fill=np.nan), np.float16)
     else:
         g1_dev = nhwc(g1)
     g2_dev = nhwc(g2) if with_g2 else None
     act_dev = nhwc(act, np.float32 if act32 else np.float16)
     gy, gz = aligned((B, h, w, c), np.float16, fill=np.nan), aligned((B, h, w, c), np.float16, fill=np.nan)
-    partial, coef = aligned((G, rows, c, 2), np.float32), aligned((G, 3 * c), np.float32)
-    gg, gb = aligned(c, np.float32), aligned(c, np.float32)
+    partial, coef = aligned((G, rows, c, 2), np.float32, fill=np.nan), aligned((G, 3 * c), np.float32, fill=np.nan)
+    gg, gb = aligned(c, np.float32, fill=np.nan), aligned(c, np.float32, fill=np.nan)
     mt, it, gm = to_aligned(mean_t), to_aligned(invstd_t), to_aligned(gamma)
     z_dev = nhwc(z)
     lib.call("ds_bn_bwd_group_f16", ptr(g1_dev), int(parity), ptr(g2_dev), ptr(act_dev), int(act32), None, None, ptr(z_dev), ptr(mt),
              ptr(it), ptr(gm), ptr(gy), ptr(partial), ptr(coef), ptr(gg), ptr(gb), ptr(gz), n_pix, h, w, c, G, 1.0 / S, None)
-    gsum = g1 + (g2 if with_g2 else 0)
-    gy_ref = r16(O.clip_bwd(act, gsum))
-    assert np.array_equal(gy.transpose(0, 3, 1, 2).astype(np.float32), gy_ref)
-    gg_ref, gb_ref = np.zeros(c), np.zeros(c)
-    gz_ref = np.empty_like(z, dtype=np.float64)
-    for m in range(G):
-        sl = slice(m * bm, (m + 1) * bm)
-        gx, g_g, g_b = O.bn_train_bwd(z[sl].astype(np.float64), mean_t[m].astype(np.float64), invstd_t[m].astype(np.float64),
-                                      gamma.astype(np.float64), gy_ref[sl].astype(np.float64))
-        gz_ref[sl] = gx
-        gg_ref += g_g
-        gb_ref += g_b
-    assert rel_l2(gz.transpose(0, 3, 1, 2), gz_ref) < 1e-3              # fp16 storage of the result
+    # O.clip_bwd + O.bn_train_bwd per member, float64, on the [pixels, C] view
+    gy_ref, gz_ref, gg_ref, gb_ref = TC.bn_bwd_ref(flat(z), flat(g1), flat(g2) if with_g2 else None, flat(act), mean_t, invstd_t,
+                                                   gamma, G)
+    assert np.array_equal(gy.reshape(-1, c).astype(np.float32), gy_ref)
+    assert rel_l2(gz.reshape(-1, c), gz_ref) < 1e-3                     # fp16 storage of the result
     assert rel_l2(gg, gg_ref / S) < 1e-5 and rel_l2(gb, gb_ref / S) < 1e-5
 
 
@@ -208,16 +210,20 @@ def test_dgrad_5x5_stride2_as_one_3x3_convolution_with_parity_classes(b, ci, co,
     out = conv16(lib, gsrc, bank, ConvShape(b, ho, wo, co, 4 * ci, 3, 1), 4 * ci).astype(np.float32)
     out = out.reshape(b, ho, wo, 2, 2, ci)
     gx, _ = O.conv2d_bwd(np.zeros((b, ci, h, w)), wt.astype(np.float64), gy.astype(np.float64), 2, 2)
-    got = np.zeros((b, ci, h, w), np.float32)
-    for hh in range(h):
-        for ww in range(w):
-            got[:, :, hh, ww] = out[:, hh >> 1, ww >> 1, hh & 1, ww & 1]
+    got = TC.parity_gather(out, h, w).transpose(0, 3, 1, 2)
     assert rel_l2(got, gx) < 1e-3
 
 
-@pytest.mark.parametrize("b,ci,co,h,w,ks,st", [(2, 64, 64, 9, 8, 3, 1), (3, 64, 128, 10, 4, 3, 1), (2, 64, 128, 11, 8, 5, 2),
-                                               (1, 128, 64, 6, 16, 5, 2), (5, 64, 64, 40, 16, 3, 1)])
-def test_wgrad_f16(b, ci, co, h, w, ks, st):
+# cus: the compute-unit count the emulator reports for this call (DS_EMUL_CUS; 2 by default, so S <= 2) -- raised so that
+# the pixel split is at least 8-way in one case ("wide": the S-way fold, several tiles per split, the last one short) and
+# clipped to the tile count in the other ("tiles": one tile per split)
+@pytest.mark.parametrize("b,ci,co,h,w,ks,st,cus,split", [_old(2, 64, 64, 9, 8, 3, 1, extra=(None, None)), _old(3, 64, 128, 10, 4, 3, 1, extra=(None, None)),
+                                                         _old(2, 64, 128, 11, 8, 5, 2, extra=(None, None)), _old(1, 128, 64, 6, 16, 5, 2, extra=(None, None)),
+                                                         _old(5, 64, 64, 40, 16, 3, 1, extra=(None, None)), (5, 64, 64, 25, 16, 3, 1, 8, "wide"),
+                                                         (3, 64, 128, 21, 16, 5, 2, 64, "tiles")])
+def test_wgrad_f16(b, ci, co, h, w, ks, st, cus, split, monkeypatch):
+    if cus:
+        monkeypatch.setenv("DS_EMUL_CUS", str(cus))
     lib = emul_lib()
     rs = np.random.RandomState(ci + co + h + ks)
     pad = ks // 2
@@ -228,7 +234,11 @@ def test_wgrad_f16(b, ci, co, h, w, ks, st):
     shp = ConvShape(b, h, w, ci, co, ks, st)
     n_ws = lib.raw("ds_conv_wgrad_f16_workspace_floats")(ctypes.byref(shp))
     assert n_ws > 0
-    ws, gw = aligned(n_ws, np.float32), aligned((co, ci, ks, ks), np.float32, fill=np.nan)
+    if split:
+        n_split = n_ws // (ks * ks * co * ci)
+        want = -(-cus // ((co // 64) * (ci // 64)))
+        assert (n_split >= 8 and n_split == want) if split == "wide" else (1 < n_split < want), (n_split, want)
+    ws, gw = aligned(n_ws, np.float32, fill=np.nan), aligned((co, ci, ks, ks), np.float32, fill=np.nan)
     x_dev, g_dev = nhwc(x), nhwc(gy)
     lib.call("ds_conv_wgrad_f16", ctypes.byref(shp), ptr(x_dev), ptr(g_dev), ptr(ws), ptr(gw), 1.0 / S, None)
     _, ref = O.conv2d_bwd(x.astype(np.float64), np.zeros((co, ci, ks, ks)), gy.astype(np.float64) / S, st, pad, need_gx=False)
