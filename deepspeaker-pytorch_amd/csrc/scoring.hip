@@ -45,18 +45,19 @@ __global__ void __launch_bounds__(256) mask_rows_kernel(char *x, const int *lens
 }
 
 // temporal mean over the utterance's own rows: pooled[b] = sum_{h < lens[b]} x[b,h] / lens[b]  (model.py:207 applied
-// to the unpadded utterance).  Rows past lens[b] are never read.
+// to the unpadded utterance).  Rows past lens[b] are never read; an utterance without rows (lens[b] <= 0) pools to 0, what
+// the mean over its rows zeroed by mask_rows_kernel gives.
 __global__ void __launch_bounds__(256) avgpool_time_masked_kernel(const float *x, const int *lens, float *pooled, int B,
                                                                   int Hr, int row_elems) {
     const int vec_per_row = row_elems >> 2;
     const long long n = (long long)B * vec_per_row;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int b = (int)(i / vec_per_row), v = (int)(i - (long long)b * vec_per_row);
-        const int len = lens[b] < Hr ? (lens[b] > 1 ? lens[b] : 1) : Hr;
+        const int len = lens[b] < Hr ? (lens[b] > 0 ? lens[b] : 0) : Hr;
         const f32x4 *src = (const f32x4 *)(x + (size_t)b * Hr * row_elems) + v;
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
         for (int h = 0; h < len; ++h) s += src[(size_t)h * vec_per_row];
-        const float hr = (float)len;
+        const float hr = (float)(len > 0 ? len : 1);
 #pragma unroll
         for (int j = 0; j < 4; ++j) s[j] = s[j] / hr;
         ((f32x4 *)(pooled + (size_t)b * row_elems))[v] = s;

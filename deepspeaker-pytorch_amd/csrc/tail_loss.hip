@@ -635,7 +635,7 @@ extern "C" int ds_mine_semihard_f32(const float *anchor, const float *d_p, const
                                     const float *cand, const long long *cand_label, float *workspace,
                                     long long *out_index, float *out_dist, int N, int M, int D, void *stream) {
     DS_REQUIRE(anchor && d_p && anchor_label && cand && cand_label && workspace && out_index, DS_ERR_NULL);
-    DS_REQUIRE(N > 0 && M > 0 && D > 0 && D <= 8192, DS_ERR_BAD_SHAPE);
+    DS_REQUIRE(N > 0 && M > 0 && D > 0 && D <= DS_MINE_MAX_D, DS_ERR_BAD_SHAPE);
     DS_REQUIRE(D % 4 == 0 && DS_ALIGNED16(cand) && DS_ALIGNED16(anchor), DS_ERR_ALIGNMENT);
     const float eps = (float)(1e-4 / (double)D);
     const int n_ctiles = ds_ceil_div(M, MINE_C);
@@ -653,7 +653,7 @@ extern "C" int ds_mine_semihard_f32(const float *anchor, const float *d_p, const
     };
     while (A > 2 && lds_of(A) > 64 * 1024) A /= 2;         // long rows: fewer anchors per workgroup fit next to the tile
     const size_t lds = lds_of(A);
-    DS_REQUIRE(lds <= 64 * 1024, DS_ERR_BAD_SHAPE);
+    DS_REQUIRE(lds <= 64 * 1024, DS_ERR_BAD_SHAPE);        // (holds for every D <= DS_MINE_MAX_D: 2 * 3584 + 256 * 36 floats)
     const int n_agroups = ds_ceil_div(N, A);
     if (A == 8)
         DS_LAUNCH(mine_semihard_kernel<8>, n_agroups * n_ctiles, 256, lds, stream, anchor, d_p, anchor_label, cand, cand_label,

@@ -451,7 +451,14 @@ int ds_scatter_add_rows_f32(const float *g, const long long *idx, float *dst, in
                             int accumulate, void *stream);
 
 /* ---- cross-GPU semi-hard negative search over an all-gathered candidate set (north_star; no
- *      reference counterpart).  out_index[i] in [0,M) or -1; out_dist may be NULL. ---- */
+ *      reference counterpart).  out_index[i] in [0,M) or -1; out_dist may be NULL.
+ *      For anchor i: among the candidates of another label, the closest one with distance > d_p[i]; without such a one the
+ *      closest of another label; the lowest index among bit-equal distances; -1 (out_dist 0) when every candidate shares
+ *      the label.  The distances are the search's own f32 sums (eps = 1e-4 / D inside the root), so a candidate whose
+ *      distance equals d_p[i] to rounding may fall on either side of the strict comparison.
+ *      D % 4 == 0 and D <= DS_MINE_MAX_D: a workgroup keeps at least two anchor rows (2 * D floats) next to its 36 KiB
+ *      candidate tile in 64 KiB of LDS; a longer row is DS_ERR_BAD_SHAPE and nothing is launched. ---- */
+#define DS_MINE_MAX_D 3584
 long long ds_mine_workspace_floats(int N, int M);
 int ds_mine_semihard_f32(const float *anchor, const float *d_p, const long long *anchor_label,
                          const float *cand, const long long *cand_label, float *workspace,
@@ -492,7 +499,9 @@ int ds_cross_entropy_bwd_f32(const float *logits, const long long *labels, const
  * Utterances of different lengths share one zero-padded batch [B,1,Tmax,64].  ds_mask_rows re-zeroes, after every
  * layer, the rows past each utterance's own extent (lens[b] rows of the [H][row_bytes] slab of image b are kept):
  * those zeros then act exactly like the utterance's own zero padding, so every kept row is bit-identical to the
- * forward of the utterance alone.  ds_avgpool_time_masked_f32 averages over the utterance's own rows. */
+ * forward of the utterance alone.  ds_avgpool_time_masked_f32 averages over the utterance's own rows.
+ * lens[b] is clamped to [0, H] by both: lens[b] <= 0 zeroes the whole image / pools to 0 (no row is read), lens[b] > H
+ * keeps / averages all H rows. */
 int ds_mask_rows(void *x, const int *lens, int B, int H, long long row_bytes, void *stream);
 int ds_avgpool_time_masked_f32(const float *x, const int *lens, float *pooled, int B, int Hr, int Wc, int C,
                                void *stream);
