@@ -1,4 +1,5 @@
-// wgrad_reduce.h -- fixed-order fold of the filter-gradient partial sums (shared by the f32 and bf16 kernels)
+// wgrad_reduce.h -- fixed-order fold of the filter-gradient partial sums (shared by wgrad_mfma_f32.hip and
+// wgrad_mfma_tr16.h, the kernel of the bf16x3 and fp16 paths)
 #pragma once
 #include <ds_device.h>
 

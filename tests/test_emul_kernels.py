@@ -313,8 +313,9 @@ WGRAD_BF16_CASES = [c for c in WGRAD_CASES if c[5] in (3, 5)] + [(4, 128, 128, 1
 
 
 @pytest.mark.parametrize("case", WGRAD_BF16_CASES)
-def test_conv_wgrad_bf16x3(case):
+def test_conv_wgrad_bf16x3(case, monkeypatch):
     """split-operand bf16 filter gradient (transposing LDS reads) against the float64 oracle"""
+    monkeypatch.setenv("DS_EMUL_CUS", "256")    # the pixel split of a 256-CU device (the emulator's default of 2: S <= 2)
     lib = emul_lib()
     b, ci, co, h, w, k, s = case
     rs = np.random.RandomState(abs(hash(case)) % 2**31)
