@@ -125,37 +125,37 @@ def _bn_bwd(eng: Engine, g1, g2, act, z, stats, gamma, reducer=None):
 FUSE_DGRAD_BN_BWD = True       # module switch for A/B runs and tests of the unfused sequence
 
 
-def _dgrad_bn_bwd(eng: Engine, shp: ConvShape, gz_up, bank_bf16, g2, z, stats, gamma, reducer=None):
-    """`_dgrad` of a 3x3 layer followed by `_bn_bwd` of the BatchNorm + clipped-ReLU layer it feeds, with the first half
-    of the latter inside the data-gradient kernel's epilogue (ds_conv_dgrad_bnbwd_bf16): the gradient never makes the
-    round trip through HBM between the two, and the mask comes from the layer's own pre-activation `z` instead of a
-    third tensor.  Returns (gy, gz, dgamma, dbeta) like `_bn_bwd`, or None where the fused kernel does not apply (a tile
-    of the launch would straddle two members, statistics not laid out as tables): the caller then runs the two steps."""
+def _fused_plan(eng: Engine, rows_entry: str, shp: ConvShape, bank_bf16, stats, c: int, n_tables: int):
+    """(members' statistics, partial rows per member) if a fused data gradient + BatchNorm backward applies, else None:
+    the switch is on, the bf16x3 bank exists, the first `n_tables` statistics of the members are rows of one table each
+    and the kernel's planner (`rows_entry`) keeps every tile of the launch inside one member."""
     if not FUSE_DGRAD_BN_BWD or bank_bf16 is None:
         return None
     members = stats if isinstance(stats, list) else [stats]
     G = len(members)
-    c = z.shape[-1]
     step = c * 4
-    if any(len(m_) < 4 for m_ in members):
+    if any(len(m_) < n_tables for m_ in members):
         return None
-    if not all(members[g][k].data_ptr() == members[0][k].data_ptr() + g * step for g in range(G) for k in range(4)):
+    if not all(members[g][k].data_ptr() == members[0][k].data_ptr() + g * step for g in range(G) for k in range(n_tables)):
         return None
-    rows = eng.lib.raw("ds_conv_dgrad_bnbwd_bf16_rows")(ctypes.byref(shp), G)
-    if rows <= 0:
-        return None
+    rows = eng.lib.raw(rows_entry)(ctypes.byref(shp), G)
+    return (members, rows) if rows > 0 else None
+
+
+def _fused_bn_bwd(eng: Engine, fused_launch, rows: int, G: int, z, mean, invstd, gamma, reducer=None):
+    """What the two fused helpers below share: the buffers, `fused_launch(gy, partial, stream)` -- the data-gradient kernel
+    that writes the masked gradient and the per-tile partial sums --, then the members' sums (through one all-reduce under
+    data parallelism) and the application.  Returns (gy, gz, dgamma, dbeta) like `_bn_bwd`."""
+    c = z.shape[-1]
     dev = z.device
     n_pix = (z.numel() // c) // G
     st = eng._stream(z)
-    mean, invstd, sc, sh = members[0]
     gy, gz = torch.empty_like(z), torch.empty_like(z)
     partial = torch.empty((G, rows, c, 2), dtype=torch.float32, device=dev)
     coef = torch.empty((G, 3 * c), dtype=torch.float32, device=dev)
     member_sums = torch.empty((2, G, c), dtype=torch.float32, device=dev)
     gg, gb = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
-    eng.lib.call("ds_conv_dgrad_bnbwd_bf16", ctypes.byref(shp), eng._p(gz_up), eng._p(bank_bf16[0]), eng._p(bank_bf16[1]),
-                 eng._p(g2), eng._p(z), eng._p(mean), eng._p(invstd), eng._p(sc), eng._p(sh), G, eng._p(gy),
-                 eng._p(partial), st)
+    fused_launch(gy, partial, st)
     if reducer is not None and reducer.active:
         sums = torch.empty((G, 2 * c + 1), dtype=torch.float64, device=dev)
         eng.lib.call("ds_partial_sum_f64_group", eng._p(partial), rows, eng._p(sums), n_pix, c, G, st)
@@ -170,66 +170,61 @@ def _dgrad_bn_bwd(eng: Engine, shp: ConvShape, gz_up, bank_bf16, g2, z, stats, g
     return gy, gz, gg, gb
 
 
+def _dgrad_bn_bwd(eng: Engine, shp: ConvShape, gz_up, bank_bf16, g2, z, stats, gamma, reducer=None):
+    """`_dgrad` of a 3x3 layer followed by `_bn_bwd` of the BatchNorm + clipped-ReLU layer it feeds, with the first half
+    of the latter inside the data-gradient kernel's epilogue (ds_conv_dgrad_bnbwd_bf16): the gradient never makes the
+    round trip through HBM between the two, and the mask comes from the layer's own pre-activation `z` instead of a
+    third tensor.  Returns (gy, gz, dgamma, dbeta) like `_bn_bwd`, or None where the fused kernel does not apply (a tile
+    of the launch would straddle two members, statistics not laid out as tables): the caller then runs the two steps."""
+    plan = _fused_plan(eng, "ds_conv_dgrad_bnbwd_bf16_rows", shp, bank_bf16, stats, z.shape[-1], 4)
+    if plan is None:
+        return None
+    members, rows = plan
+    G = len(members)
+    mean, invstd, sc, sh = members[0]
+
+    def fused_launch(gy, partial, st):
+        eng.lib.call("ds_conv_dgrad_bnbwd_bf16", ctypes.byref(shp), eng._p(gz_up), eng._p(bank_bf16[0]), eng._p(bank_bf16[1]),
+                     eng._p(g2), eng._p(z), eng._p(mean), eng._p(invstd), eng._p(sc), eng._p(sh), G, eng._p(gy),
+                     eng._p(partial), st)
+    return _fused_bn_bwd(eng, fused_launch, rows, G, z, mean, invstd, gamma, reducer)
+
+
 def _dgrad_s2_bn_bwd(eng: Engine, shp: ConvShape, gz_up, bank_bf16, act, z, stats, gamma, reducer=None):
     """`_dgrad` of a 5x5 stride-2 layer followed by `_bn_bwd` of the BasicBlock output it feeds (bn2 + residual + clip of
     the previous stage), fused like `_dgrad_bn_bwd` (ds_conv_dgrad_s2_bnbwd_bf16): the four parity-class launches mask
     with the stored activation `act`, sum and write gy.  Returns (gy, gz, dgamma, dbeta) or None (not applicable)."""
-    if not FUSE_DGRAD_BN_BWD or bank_bf16 is None:
+    plan = _fused_plan(eng, "ds_conv_dgrad_s2_bnbwd_bf16_rows", shp, bank_bf16, stats, z.shape[-1], 2)
+    if plan is None:
         return None
-    members = stats if isinstance(stats, list) else [stats]
+    members, rows = plan
     G = len(members)
-    c = z.shape[-1]
-    step = c * 4
-    if not all(members[g][k].data_ptr() == members[0][k].data_ptr() + g * step for g in range(G) for k in range(2)):
-        return None
-    rows = eng.lib.raw("ds_conv_dgrad_s2_bnbwd_bf16_rows")(ctypes.byref(shp), G)
-    if rows <= 0:
-        return None
-    dev = z.device
-    n_pix = (z.numel() // c) // G
-    st = eng._stream(z)
     mean, invstd = members[0][0], members[0][1]
-    gy, gz = torch.empty_like(z), torch.empty_like(z)
-    partial = torch.empty((G, rows, c, 2), dtype=torch.float32, device=dev)
-    coef = torch.empty((G, 3 * c), dtype=torch.float32, device=dev)
-    member_sums = torch.empty((2, G, c), dtype=torch.float32, device=dev)
-    gg, gb = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
-    eng.lib.call("ds_conv_dgrad_s2_bnbwd_bf16", ctypes.byref(shp), eng._p(gz_up), eng._p(bank_bf16[0]),
-                 eng._p(bank_bf16[1]), eng._p(act), eng._p(z), eng._p(mean), eng._p(invstd), G, eng._p(gy),
-                 eng._p(partial), st)
-    if reducer is not None and reducer.active:
-        sums = torch.empty((G, 2 * c + 1), dtype=torch.float64, device=dev)
-        eng.lib.call("ds_partial_sum_f64_group", eng._p(partial), rows, eng._p(sums), n_pix, c, G, st)
-        reducer.all_reduce_sum_(sums)
-        eng.lib.call("ds_bn_bwd_group_apply_f32", eng._p(sums), eng._p(gy), eng._p(z), eng._p(mean), eng._p(invstd),
-                     eng._p(gamma.detach()), eng._p(coef), eng._p(member_sums), eng._p(gg), eng._p(gb), eng._p(gz),
-                     n_pix, c, G, st)
-    else:
-        eng.lib.call("ds_bn_bwd_group_finish_f32", eng._p(partial), rows, eng._p(gy), eng._p(z), eng._p(mean),
-                     eng._p(invstd), eng._p(gamma.detach()), eng._p(coef), eng._p(member_sums), eng._p(gg), eng._p(gb),
-                     eng._p(gz), n_pix, c, G, st)
-    return gy, gz, gg, gb
+
+    def fused_launch(gy, partial, st):
+        eng.lib.call("ds_conv_dgrad_s2_bnbwd_bf16", ctypes.byref(shp), eng._p(gz_up), eng._p(bank_bf16[0]),
+                     eng._p(bank_bf16[1]), eng._p(act), eng._p(z), eng._p(mean), eng._p(invstd), G, eng._p(gy),
+                     eng._p(partial), st)
+    return _fused_bn_bwd(eng, fused_launch, rows, G, z, mean, invstd, gamma, reducer)
+
+
+def _wgrad_call(eng: Engine, workspace_entry: str, entry: str, shp: ConvShape, x, gz, out, *tail):
+    """One filter-gradient launch into `out`: the kernel's workspace is asked for, checked and allocated here.  `tail`:
+    the entry point's arguments between the output and the stream (fc bins, 1 / loss scale)."""
+    n_ws = eng.lib.raw(workspace_entry)(ctypes.byref(shp))
+    if n_ws <= 0:
+        raise RuntimeError(f"{workspace_entry} failed: {n_ws}")
+    ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+    eng.lib.call(entry, ctypes.byref(shp), eng._p(x), eng._p(gz), eng._p(ws), eng._p(out), *tail, eng._stream(x))
+    return out
 
 
 def _wgrad(eng: Engine, shp: ConvShape, x, gz, out_shape, fc_f: int = 0, x3: bool = False, out=None):
     """filter gradient into `out` (a contiguous view of a gradient bucket) or a fresh tensor"""
-    if x3 and shp.KS in (3, 5) and shp.Cin % 64 == 0:      # split-operand bf16 matrix cores
-        n_ws = eng.lib.raw("ds_conv_wgrad_bf16_workspace_floats")(ctypes.byref(shp))
-        if n_ws <= 0:
-            raise RuntimeError(f"ds_conv_wgrad_bf16_workspace_floats failed: {n_ws}")
-        ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
-        gw = out if out is not None else torch.empty(out_shape, dtype=torch.float32, device=x.device)
-        eng.lib.call("ds_conv_wgrad_bf16", ctypes.byref(shp), eng._p(x), eng._p(gz), eng._p(ws), eng._p(gw),
-                     eng._stream(x))
-        return gw
-    n_ws = eng.lib.raw("ds_conv_wgrad_workspace_floats")(ctypes.byref(shp))
-    if n_ws <= 0:
-        raise RuntimeError(f"ds_conv_wgrad_workspace_floats failed: {n_ws}")
-    ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
     gw = out if out is not None else torch.empty(out_shape, dtype=torch.float32, device=x.device)
-    eng.lib.call("ds_conv_wgrad_f32", ctypes.byref(shp), eng._p(x), eng._p(gz), eng._p(ws), eng._p(gw), fc_f,
-                 eng._stream(x))
-    return gw
+    if x3 and shp.KS in (3, 5) and shp.Cin % 64 == 0:      # split-operand bf16 matrix cores
+        return _wgrad_call(eng, "ds_conv_wgrad_bf16_workspace_floats", "ds_conv_wgrad_bf16", shp, x, gz, gw)
+    return _wgrad_call(eng, "ds_conv_wgrad_workspace_floats", "ds_conv_wgrad_f32", shp, x, gz, gw, fc_f)
 
 
 def _dgrad(eng: Engine, shp: ConvShape, gz, w_dgrad, w_dgrad_bf16=None):
@@ -335,15 +330,25 @@ class _GradBuckets:
         self.work = []
 
 
-def backward_train(eng: Engine, bn_weights: Dict[str, torch.Tensor], pw: PackedWeights, saved: SavedForward,
-                   ge: torch.Tensor, reducer=None, precision: str = "f32",
-                   reduce_gradients: bool = False, overlap_filter_gradients=None) -> Dict[str, torch.Tensor]:
-    """Parameter gradients (reference key names, reference shapes) given dL/d(embedding) `ge` [B,512].
-    precision "bf16x3": data and filter gradients of the 3x3 / 5x5 layers run on the bf16 matrix cores with
-    split operands; conv1 and fc stay on the f32 matrix cores.  `reduce_gradients` (data parallelism): the
-    per-stage gradient buckets are all-reduced over `reducer` as the pass produces them, overlapped with the rest
-    of the pass; the returned gradients are then the global sums.  `overlap_filter_gradients`: see _FilterGradLane."""
-    x3 = precision == "bf16x3"
+def _backward_walk(eng: Engine, ar, bn_weights: Dict[str, torch.Tensor], pw: PackedWeights, saved: SavedForward,
+                   ge: torch.Tensor, reducer, reduce_gradients: bool, overlap_filter_gradients):
+    """The layer sequence of every backward pass, the counterpart of Engine._train_walk: the f32 tail (l2-norm, fc,
+    temporal mean), then per stage, last first, bn2 -> conv2's filter gradient -> conv2's data gradient + bn1 -> conv1's
+    filter gradient -> conv1's data gradient + bn_i (the residual's gradient joins there) -> conv_i's filter gradient ->
+    conv_i's data gradient towards the stage below.  This loop owns the order, the shapes, the saved-tensor lookups, the
+    gradient buckets with their exchange and the filter-gradient lane; `ar` is the pass's arithmetic (_F32Class here,
+    train_f16._F16):
+
+      ar.head(g)                                    the f32 gradient of the last stage's output -> what its bn2 step takes
+      ar.bn2(handed, z, stats, gamma, hw)           -> (g_out, gz, dgamma, dbeta); `handed` comes from head / dgrad_s2
+      ar.dgrad_bn(shp, gz, sw, conv, g_out, act, z, stats, gamma)   the 3x3 data gradient of `sw.<conv>` and the BatchNorm
+                                                    backward of the layer it feeds (+ g_out) -> (gz, dgamma, dbeta)
+      ar.wgrad(shp, x, gz, out)                     one layer's filter gradient into its bucket view
+      ar.dgrad_s2(shp, gz, sw, x_in, z, stats, gamma)   the 5x5 stride-2 data gradient -> what the bn2 step of the stage
+                                                    below takes (x_in IS that stage's output: the mask of its clip)
+      ar.exchange_before_dgrad_s2                   on which side of that launch a stage's bucket goes to the reducer
+
+    Returns (parameter gradients, the buckets)."""
     lane = _FilterGradLane(ge.device, OVERLAP_FILTER_GRADIENTS if overlap_filter_gradients is None else overlap_filter_gradients)
     lib = eng.lib
     grads: Dict[str, torch.Tensor] = {}
@@ -368,8 +373,7 @@ def backward_train(eng: Engine, bn_weights: Dict[str, torch.Tensor], pw: PackedW
     gb = buckets.views["model.fc.bias"]
     lib.call("ds_colsum_f32", eng._p(gf), eng._p(gb), B, n_out, st)
     grads["model.fc.bias"] = gb
-    c_last = STAGE_CHANNELS[n_stages - 1]
-    f_bins = k // c_last
+    f_bins = k // STAGE_CHANNELS[n_stages - 1]
     grads["model.fc.weight"] = _wgrad(eng, ConvShape(1, B, 1, k, n_out, 1, 1), pooled, gf, (n_out, k), f_bins,
                                       out=buckets.views["model.fc.weight"])
     buckets.done(n_stages)
@@ -382,61 +386,95 @@ def backward_train(eng: Engine, bn_weights: Dict[str, torch.Tensor], pw: PackedW
     _, hr, wc, c = out.shape
     g = torch.empty_like(out)
     lib.call("ds_avgpool_time_bwd_f32", eng._p(gpooled), eng._p(out), eng._p(g), B, hr, wc, c, st)
-    g_is_masked = True
-    pre = None
+    handed = ar.head(g)
+
+    def bn(name):
+        return saved.raws[name], saved.stats[name], bn_weights[name]
+
+    def filter_gradient(name, shp, x, gz):
+        grads[name] = lane.run(lambda: ar.wgrad(shp, x, gz, buckets.views[name]), gz)
+
     for s in reversed(range(n_stages)):
         i, c = s + 1, STAGE_CHANNELS[s]
         h, w = saved.dims[s]
         cin = 1 if s == 0 else STAGE_CHANNELS[s - 1]
-        a_act, b_act, c_act = (saved.acts[f"stage{i}.{t}"] for t in "abc")
+        sw = pw.stages[s]
+        a_act, b_act = saved.acts[f"stage{i}.a"], saved.acts[f"stage{i}.b"]
         shp3 = ConvShape(B, h, w, c, c, 3, 1)
         # out = clip(bn2(conv2(y)) + r)            (model.py:73-80)
         name = f"model.layer{i}.0.bn2"
-        if pre is not None:       # the stage above already ran this step inside its 5x5 data gradient
-            g_out, gz, gg, gbeta = pre
-            pre = None
-        else:
-            g_out, gz, gg, gbeta = _bn_bwd(eng, g, None, None if g_is_masked else c_act, saved.raws[name],
-                                           saved.stats[name], bn_weights[name], reducer)
-        grads[name + ".weight"], grads[name + ".bias"] = gg, gbeta
-        grads[f"model.layer{i}.0.conv2.weight"] = lane.run(
-            lambda gz=gz: _wgrad(eng, shp3, b_act, gz, (c, c, 3, 3), x3=x3,
-                                 out=buckets.views[f"model.layer{i}.0.conv2.weight"]), gz)
+        g_out, gz, grads[name + ".weight"], grads[name + ".bias"] = ar.bn2(handed, *bn(name), (h, w))
+        filter_gradient(f"model.layer{i}.0.conv2.weight", shp3, b_act, gz)
         # y = clip(bn1(conv1(r)))                  (model.py:69-71): conv2's data gradient + bn1's backward
         name = f"model.layer{i}.0.bn1"
-        bank = pw.stages[s].l_conv2_dgrad_bf16 if x3 else None
-        fused = _dgrad_bn_bwd(eng, shp3, gz, bank, None, saved.raws[name], saved.stats[name], bn_weights[name], reducer)
-        if fused is None:
-            g_y = _dgrad(eng, shp3, gz, pw.stages[s].l_conv2_dgrad, bank)
-            fused = _bn_bwd(eng, g_y, None, b_act, saved.raws[name], saved.stats[name], bn_weights[name], reducer)
-        _, gz, gg, gbeta = fused
-        grads[name + ".weight"], grads[name + ".bias"] = gg, gbeta
-        grads[f"model.layer{i}.0.conv1.weight"] = lane.run(
-            lambda gz=gz: _wgrad(eng, shp3, a_act, gz, (c, c, 3, 3), x3=x3,
-                                 out=buckets.views[f"model.layer{i}.0.conv1.weight"]), gz)
+        gz, grads[name + ".weight"], grads[name + ".bias"] = ar.dgrad_bn(shp3, gz, sw, "l_conv2", None, b_act, *bn(name))
+        filter_gradient(f"model.layer{i}.0.conv1.weight", shp3, a_act, gz)
         # r = clip(bn_i(conv_i(x)));  dL/dr = conv-path + residual path   (model.py:187-189, 67, 79)
         name = f"model.bn{i}"
-        bank = pw.stages[s].l_conv1_dgrad_bf16 if x3 else None
-        fused = _dgrad_bn_bwd(eng, shp3, gz, bank, g_out, saved.raws[name], saved.stats[name], bn_weights[name], reducer)
-        if fused is None:
-            g_r = _dgrad(eng, shp3, gz, pw.stages[s].l_conv1_dgrad, bank)
-            fused = _bn_bwd(eng, g_r, g_out, a_act, saved.raws[name], saved.stats[name], bn_weights[name], reducer)
-        _, gz, gg, gbeta = fused
-        grads[name + ".weight"], grads[name + ".bias"] = gg, gbeta
+        gz, grads[name + ".weight"], grads[name + ".bias"] = ar.dgrad_bn(shp3, gz, sw, "l_conv1", g_out, a_act, *bn(name))
         h_in, w_in = (saved.x.shape[2], saved.x.shape[3]) if s == 0 else saved.dims[s - 1]
         shp5 = ConvShape(B, h_in, w_in, cin, c, 5, 2)
         x_in = saved.x if s == 0 else saved.acts[f"stage{s}.c"]
-        grads[f"model.conv{i}.weight"] = lane.run(
-            lambda gz=gz: _wgrad(eng, shp5, x_in, gz, (c, cin, 5, 5), x3=x3, out=buckets.views[f"model.conv{i}.weight"]), gz)
-        lane.run(lambda: buckets.done(s))       # this stage's three filter gradients are enqueued: reduce them now
+        filter_gradient(f"model.conv{i}.weight", shp5, x_in, gz)
+        # this stage's three filter gradients are enqueued: reduce them now.  (The f32-class pass forks the exchange off
+        # before the stride-2 data gradient is enqueued, the fp16 pass after it -- the lane orders the exchange behind
+        # whatever the main stream holds at the fork, so the side is part of each pass's schedule and is kept.)
+        if ar.exchange_before_dgrad_s2:
+            lane.run(lambda: buckets.done(s))
         if s > 0:
-            below = f"model.layer{s}.0.bn2"                 # out = clip(bn2(conv2(y)) + r) of the stage below
-            bank = pw.stages[s].conv_dgrad_bf16 if x3 else None
-            pre = _dgrad_s2_bn_bwd(eng, shp5, gz, bank, x_in, saved.raws[below], saved.stats[below], bn_weights[below],
-                                   reducer)
-            if pre is None:
-                g = _dgrad(eng, shp5, gz, pw.stages[s].conv_dgrad, bank)   # unmasked: the next bn2 step masks it
-                g_is_masked = False
+            handed = ar.dgrad_s2(shp5, gz, sw, x_in, *bn(f"model.layer{s}.0.bn2"))
+        if not ar.exchange_before_dgrad_s2:
+            lane.run(lambda: buckets.done(s))
     lane.join()
     buckets.finish()
+    return grads, buckets
+
+
+class _F32Class:
+    """The f32-class arithmetic of `_backward_walk` (f32, or bf16x3: data and filter gradients of the 3x3 / 5x5 layers on
+    the bf16 matrix cores with split operands).  A stage hands the bn2 step below it either the finished
+    (gy, gz, dgamma, dbeta) of the fused stride-2 kernel or (gradient, the activation that still has to mask it)."""
+    exchange_before_dgrad_s2 = True
+
+    def __init__(self, eng: Engine, x3: bool, reducer):
+        self.eng, self.x3, self.reducer = eng, x3, reducer
+
+    def head(self, g):
+        return g, None                  # ds_avgpool_time_bwd_f32 applied the last clip's mask
+
+    def bn2(self, handed, z, stats, gamma, hw):
+        if len(handed) == 4:            # the stage above already ran this step inside its 5x5 data gradient
+            return handed
+        g, mask_act = handed
+        return _bn_bwd(self.eng, g, None, mask_act, z, stats, gamma, self.reducer)
+
+    def dgrad_bn(self, shp, gz, sw, conv, g_out, act, z, stats, gamma):
+        bank = getattr(sw, conv + "_dgrad_bf16") if self.x3 else None
+        fused = _dgrad_bn_bwd(self.eng, shp, gz, bank, g_out, z, stats, gamma, self.reducer)
+        if fused is None:
+            g = _dgrad(self.eng, shp, gz, getattr(sw, conv + "_dgrad"), bank)
+            fused = _bn_bwd(self.eng, g, g_out, act, z, stats, gamma, self.reducer)
+        return fused[1:]
+
+    def wgrad(self, shp, x, gz, out):
+        return _wgrad(self.eng, shp, x, gz, None, x3=self.x3, out=out)
+
+    def dgrad_s2(self, shp, gz, sw, x_in, z, stats, gamma):
+        bank = sw.conv_dgrad_bf16 if self.x3 else None
+        fused = _dgrad_s2_bn_bwd(self.eng, shp, gz, bank, x_in, z, stats, gamma, self.reducer)
+        if fused is not None:
+            return fused
+        return _dgrad(self.eng, shp, gz, sw.conv_dgrad, bank), x_in        # unmasked: the next bn2 step masks it
+
+
+def backward_train(eng: Engine, bn_weights: Dict[str, torch.Tensor], pw: PackedWeights, saved: SavedForward,
+                   ge: torch.Tensor, reducer=None, precision: str = "f32",
+                   reduce_gradients: bool = False, overlap_filter_gradients=None) -> Dict[str, torch.Tensor]:
+    """Parameter gradients (reference key names, reference shapes) given dL/d(embedding) `ge` [B,512].
+    precision "bf16x3": data and filter gradients of the 3x3 / 5x5 layers run on the bf16 matrix cores with
+    split operands; conv1 and fc stay on the f32 matrix cores.  `reduce_gradients` (data parallelism): the
+    per-stage gradient buckets are all-reduced over `reducer` as the pass produces them, overlapped with the rest
+    of the pass; the returned gradients are then the global sums.  `overlap_filter_gradients`: see _FilterGradLane."""
+    grads, _ = _backward_walk(eng, _F32Class(eng, precision == "bf16x3", reducer), bn_weights, pw, saved, ge, reducer,
+                              reduce_gradients, overlap_filter_gradients)
     return grads

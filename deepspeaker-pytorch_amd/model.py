@@ -172,7 +172,7 @@ class HeadPack:
 def _head_backward(eng, pack: HeadPack, x, gp):
     """(dx, dW, db) of logits = x W^T + b given the padded logits gradient gp [M, Np]"""
     from ._native import ConvShape
-    import ctypes
+    from .backward import _wgrad
     m, k = x.shape
     st = eng._stream(x)
     ws = torch.empty(eng.lib.raw("ds_fc_workspace_floats")(m, pack.npad, k), dtype=torch.float32, device=x.device)
@@ -180,10 +180,7 @@ def _head_backward(eng, pack: HeadPack, x, gp):
     eng.lib.call("ds_fc_l2norm_fwd_f32", eng._p(gp), eng._p(pack.wd), None, eng._p(ws), eng._p(gx), None, m, pack.npad, k,
                  1.0, 0.0, st)                                      # dx = g Wpad
     shp = ConvShape(1, m, 1, k, pack.npad, 1, 1)                    # dW = g^T x: a 1x1 "convolution" over the M rows
-    ws2 = torch.empty(eng.lib.raw("ds_conv_wgrad_workspace_floats")(ctypes.byref(shp)), dtype=torch.float32,
-                      device=x.device)
-    gw = torch.empty((pack.npad, k), dtype=torch.float32, device=x.device)
-    eng.lib.call("ds_conv_wgrad_f32", ctypes.byref(shp), eng._p(x), eng._p(gp), eng._p(ws2), eng._p(gw), 0, st)
+    gw = _wgrad(eng, shp, x, gp, (pack.npad, k))
     gb = torch.empty(pack.npad, dtype=torch.float32, device=x.device)
     eng.lib.call("ds_colsum_f32", eng._p(gp), eng._p(gb), m, pack.npad, st)
     return gx, gw[:pack.n], gb[:pack.n]

@@ -2,7 +2,8 @@
 
 Same function as the f32-class step (`Engine.forward_train_group` + `backward.backward_train`, i.e. the reference's
 `out_a, out_p, out_n = model(data_a), model(data_p), model(data_n)`; `loss.backward()` -- train_triplet.py:215-223), other
-arithmetic and other bytes:
+arithmetic and other bytes (the layer walks are shared: `Engine._train_walk`, `backward._backward_walk`; this file supplies
+the per-layer routines):
 
 * every activation, pre-activation and gradient tensor is fp16 in HBM (the network input, the last stage's output and
   everything behind it -- pooling, projection, l2-norm, loss -- stay f32);
@@ -25,14 +26,13 @@ BatchNorm layer and direction carrying all members' sums, f32 gradient buckets p
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, List, Optional
 
 import torch
 
-from ._native import ConvShape, DS_EPI_OUT_F16, DS_EPI_OUT_F32
-from .engine import (ALPHA, BN_EPS, BN_MOMENTUM, L2_EPS, STAGE_CHANNELS, BNParams, Engine, PackedWeights, SavedForward,
-                     _clip_flags)
+from ._native import DS_EPI_OUT_F16, DS_EPI_OUT_F32
+from .backward import _backward_walk, _wgrad_call
+from .engine import BN_EPS, BN_MOMENTUM, BNParams, Engine, PackedWeights, SavedForward, _clip_flags
 
 DEFAULT_LOSS_SCALE = 1024.0
 
@@ -140,22 +140,42 @@ def _bn_bwd(eng: Engine, g1, g1_parity, g2, act, z16, tables, gamma, G: int, hw,
     return gy, gz, gg, gb
 
 
-def _wgrad(eng: Engine, shp: ConvShape, x16, gz16, out, inv_scale: float):
-    n_ws = eng.lib.raw("ds_conv_wgrad_f16_workspace_floats")(ctypes.byref(shp))
-    if n_ws <= 0:
-        raise RuntimeError(f"ds_conv_wgrad_f16_workspace_floats failed: {n_ws}")
-    ws = torch.empty(n_ws, dtype=torch.float32, device=x16.device)
-    eng.lib.call("ds_conv_wgrad_f16", ctypes.byref(shp), eng._p(x16), eng._p(gz16), eng._p(ws), eng._p(out),
-                 float(inv_scale), eng._stream(x16))
-    return out
+class _F16:
+    """The fp16 arithmetic of `backward._backward_walk`: fp16 gradient tensors holding `loss_scale` * g, data gradients on
+    the forward's fp16 convolution kernel over the flipped banks.  A stage hands the bn2 step below it (gradient, parity
+    layout?, the activation that still has to mask it)."""
+    exchange_before_dgrad_s2 = False
 
+    def __init__(self, eng: Engine, G: int, loss_scale: float, reducer):
+        self.eng, self.G, self.loss_scale, self.inv, self.reducer = eng, G, float(loss_scale), 1.0 / float(loss_scale), reducer
 
-def _wgrad_c1(eng: Engine, shp: ConvShape, x32, gz16, out, inv_scale: float):
-    n_ws = eng.lib.raw("ds_conv_wgrad_workspace_floats")(ctypes.byref(shp))
-    ws = torch.empty(n_ws, dtype=torch.float32, device=x32.device)
-    eng.lib.call("ds_conv_wgrad_c1_f16", ctypes.byref(shp), eng._p(x32), eng._p(gz16), eng._p(ws), eng._p(out),
-                 float(inv_scale), eng._stream(x32))
-    return out
+    def head(self, g32):
+        g = torch.empty(g32.shape, dtype=torch.float16, device=g32.device)
+        self.eng.lib.call("ds_scale_cast_f32_to_f16", self.eng._p(g32), self.eng._p(g), g32.numel(), self.loss_scale,
+                          self.eng._stream(g32))
+        return g, False, None           # ds_avgpool_time_bwd_f32 applied the last clip's mask
+
+    def bn2(self, handed, z, tables, gamma, hw):
+        g, parity, mask_act = handed
+        return _bn_bwd(self.eng, g, parity, None, mask_act, z, tables, gamma, self.G, hw, self.inv, reducer=self.reducer)
+
+    def dgrad_bn(self, shp, gz, sw, conv, g_out, act, z, tables, gamma):
+        g = self.eng.conv_f16(gz, getattr(sw, conv + "_dgrad_f16"), shp.B, shp.H, shp.W, shp.Cout, shp.Cin, 3, 1)
+        # (no residual was added before this clip: its mask is re-derived from z; the masked gradient is stored only where
+        # the residual's gradient g_out has to be added to it)
+        return _bn_bwd(self.eng, g, False, g_out, None, z, tables, gamma, self.G, (shp.H, shp.W), self.inv, mask_from_z=True,
+                       want_gy=g_out is not None, reducer=self.reducer)[1:]
+
+    def wgrad(self, shp, x, gz16, out):
+        if shp.Cin == 1:                # conv1: f32 input
+            return _wgrad_call(self.eng, "ds_conv_wgrad_workspace_floats", "ds_conv_wgrad_c1_f16", shp, x, gz16, out, self.inv)
+        return _wgrad_call(self.eng, "ds_conv_wgrad_f16_workspace_floats", "ds_conv_wgrad_f16", shp, x, gz16, out, self.inv)
+
+    def dgrad_s2(self, shp, gz, sw, x_in, z, tables, gamma):
+        # dL/d(stage-below output): ONE 3x3 convolution over dL/dz whose 4 cin output channels are the parity classes
+        # of the stride-2 data gradient; the layer below reads that layout in place and masks it itself
+        B, h, w, c = gz.shape
+        return self.eng.conv_f16(gz, sw.conv_dgrad_f16, B, h, w, c, 4 * shp.Cin, 3, 1), True, x_in
 
 
 def backward_train_f16(eng: Engine, bn_weights: Dict[str, torch.Tensor], pw: PackedWeights, saved: SavedForward,
@@ -173,92 +193,9 @@ def backward_train_f16(eng: Engine, bn_weights: Dict[str, torch.Tensor], pw: Pac
     (the static loss scale was too large for this step); never cleared and never read by the host here -- a step may be
     several passes (three `model(x)` calls, gradient accumulation), so the flag is cleared where it is CONSUMED: by the
     fused optimizer after its update (optim._FusedBase._consume_skip)."""
-    from .backward import OVERLAP_FILTER_GRADIENTS, _FilterGradLane, _GradBuckets, _wgrad as _wgrad_f32
-    lib = eng.lib
-    lane = _FilterGradLane(ge.device, OVERLAP_FILTER_GRADIENTS if overlap_filter_gradients is None else overlap_filter_gradients)
-    inv = 1.0 / float(loss_scale)
-    grads: Dict[str, torch.Tensor] = {}
-    n_stages = len(pw.stages)
     G = saved.stats["model.bn1"].shape[1]
-    shapes = {n_stages: {"model.fc.weight": tuple(saved.fc_out.shape[1:]) + (saved.pooled.shape[1],),
-                         "model.fc.bias": (saved.fc_out.shape[1],)}}
-    for s_ in range(n_stages):
-        i_, c_ = s_ + 1, STAGE_CHANNELS[s_]
-        cin_ = 1 if s_ == 0 else STAGE_CHANNELS[s_ - 1]
-        shapes[s_] = {f"model.layer{i_}.0.conv2.weight": (c_, c_, 3, 3), f"model.layer{i_}.0.conv1.weight": (c_, c_, 3, 3),
-                      f"model.conv{i_}.weight": (c_, cin_, 5, 5)}
-    buckets = _GradBuckets(shapes, ge.device, reducer if reduce_gradients else None)
-    f = saved.fc_out
-    B, n_out = f.shape
-    st = eng._stream(f)
-    # ---- f32 tail: l2-norm x alpha, fc, temporal mean + the last clip (model.py:205-213), as in backward_train ----
-    gf = torch.empty_like(f)
-    lib.call("ds_l2norm_scale_bwd_f32", eng._p(f), eng._p(ge), eng._p(gf), B, n_out, ALPHA, L2_EPS, st)
-    pooled = saved.pooled
-    k = pooled.shape[1]
-    gb = buckets.views["model.fc.bias"]
-    lib.call("ds_colsum_f32", eng._p(gf), eng._p(gb), B, n_out, st)
-    grads["model.fc.bias"] = gb
-    c_last = STAGE_CHANNELS[n_stages - 1]
-    grads["model.fc.weight"] = _wgrad_f32(eng, ConvShape(1, B, 1, k, n_out, 1, 1), pooled, gf, (n_out, k), k // c_last,
-                                          out=buckets.views["model.fc.weight"])
-    buckets.done(n_stages)
-    ws = torch.empty(lib.raw("ds_fc_workspace_floats")(B, n_out, k), dtype=torch.float32, device=f.device)
-    gpooled = torch.empty((B, k), dtype=torch.float32, device=f.device)
-    lib.call("ds_fc_l2norm_fwd_f32", eng._p(gf), eng._p(pw.fc_dgrad), None, eng._p(ws), eng._p(gpooled), None, B,
-             n_out, k, 1.0, 0.0, st)
-    out = saved.acts[f"stage{n_stages}.c"]                  # f32
-    _, hr, wc, c = out.shape
-    g32 = torch.empty_like(out)
-    lib.call("ds_avgpool_time_bwd_f32", eng._p(gpooled), eng._p(out), eng._p(g32), B, hr, wc, c, st)
-    g = torch.empty(out.shape, dtype=torch.float16, device=out.device)
-    lib.call("ds_scale_cast_f32_to_f16", eng._p(g32), eng._p(g), g32.numel(), float(loss_scale), st)
-    g_parity, g_masked = False, True
-    for s in reversed(range(n_stages)):
-        i, c = s + 1, STAGE_CHANNELS[s]
-        h, w = saved.dims[s]
-        cin = 1 if s == 0 else STAGE_CHANNELS[s - 1]
-        a_act, b_act, c_act = (saved.acts[f"stage{i}.{t}"] for t in "abc")
-        sw = pw.stages[s]
-        shp3 = ConvShape(B, h, w, c, c, 3, 1)
-        # out = clip(bn2(conv2(y)) + r)            (model.py:73-80)
-        name = f"model.layer{i}.0.bn2"
-        g_out, gz, gg, gbeta = _bn_bwd(eng, g, g_parity, None, None if g_masked else c_act, saved.raws[name],
-                                       saved.stats[name], bn_weights[name], G, (h, w), inv, reducer=reducer)
-        grads[name + ".weight"], grads[name + ".bias"] = gg, gbeta
-        grads[f"model.layer{i}.0.conv2.weight"] = lane.run(
-            lambda gz=gz: _wgrad(eng, shp3, b_act, gz, buckets.views[f"model.layer{i}.0.conv2.weight"], inv), gz)
-        # y = clip(bn1(conv1(r)))                  (model.py:69-71)
-        name = f"model.layer{i}.0.bn1"
-        g_y = eng.conv_f16(gz, sw.l_conv2_dgrad_f16, B, h, w, c, c, 3, 1)
-        # (no residual was added before this clip: its mask is re-derived from z; nobody else needs the masked gradient)
-        _, gz, gg, gbeta = _bn_bwd(eng, g_y, False, None, None, saved.raws[name], saved.stats[name], bn_weights[name], G,
-                                   (h, w), inv, mask_from_z=True, want_gy=False, reducer=reducer)
-        grads[name + ".weight"], grads[name + ".bias"] = gg, gbeta
-        grads[f"model.layer{i}.0.conv1.weight"] = lane.run(
-            lambda gz=gz: _wgrad(eng, shp3, a_act, gz, buckets.views[f"model.layer{i}.0.conv1.weight"], inv), gz)
-        # r = clip(bn_i(conv_i(x)));  dL/dr = conv path + residual path   (model.py:187-189, 67, 79)
-        name = f"model.bn{i}"
-        g_r = eng.conv_f16(gz, sw.l_conv1_dgrad_f16, B, h, w, c, c, 3, 1)
-        _, gz, gg, gbeta = _bn_bwd(eng, g_r, False, g_out, None, saved.raws[name], saved.stats[name], bn_weights[name], G,
-                                   (h, w), inv, mask_from_z=True, reducer=reducer)
-        grads[name + ".weight"], grads[name + ".bias"] = gg, gbeta
-        h_in, w_in = (saved.x.shape[2], saved.x.shape[3]) if s == 0 else saved.dims[s - 1]
-        shp5 = ConvShape(B, h_in, w_in, cin, c, 5, 2)
-        if s == 0:
-            grads["model.conv1.weight"] = lane.run(
-                lambda gz=gz: _wgrad_c1(eng, shp5, saved.x, gz, buckets.views["model.conv1.weight"], inv), gz)
-        else:
-            x_in = saved.acts[f"stage{s}.c"]
-            grads[f"model.conv{i}.weight"] = lane.run(
-                lambda gz=gz, x_in=x_in: _wgrad(eng, shp5, x_in, gz, buckets.views[f"model.conv{i}.weight"], inv), gz)
-            # dL/d(stage-below output): ONE 3x3 convolution over dL/dz whose 4 cin output channels are the parity classes
-            # of the stride-2 data gradient; the layer below reads that layout in place and masks it itself
-            g = eng.conv_f16(gz, sw.conv_dgrad_f16, B, h, w, c, 4 * cin, 3, 1)
-            g_parity, g_masked = True, False
-        lane.run(lambda: buckets.done(s))       # this stage's three filter gradients are enqueued: reduce them now
-    lane.join()
-    buckets.finish()
+    grads, buckets = _backward_walk(eng, _F16(eng, G, loss_scale, reducer), bn_weights, pw, saved, ge, reducer,
+                                    reduce_gradients, overlap_filter_gradients)
     if overflow_flag is not None:
         # Loss scaling is STATIC (`loss_scale`), and ds_scale_cast_f32_to_f16 does not saturate: a scaled gradient beyond
         # fp16's 65504 is an inf in the gradient tensors, then NaN in the BatchNorm-backward sums and in every filter
@@ -267,5 +204,5 @@ def backward_train_f16(eng: Engine, bn_weights: Dict[str, torch.Tensor], pw: Pac
         # it; under data parallelism the buckets are already the global sums, so every rank raises the same flag.  The
         # flag stays on the device: the fused optimizers read it there (optim._FusedBase.skip_flag).
         for flat in buckets.flat.values():
-            lib.call("ds_nonfinite_flag_f32", eng._p(flat), flat.numel(), eng._p(overflow_flag), st)
+            eng.lib.call("ds_nonfinite_flag_f32", eng._p(flat), flat.numel(), eng._p(overflow_flag), eng._stream(flat))
     return grads
