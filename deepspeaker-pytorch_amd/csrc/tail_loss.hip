@@ -6,14 +6,9 @@
 // One 64-lane wavefront owns one embedding row; row reductions are wave shuffles.
 #include <ds_device.h>
 #include "ds_common.h"
+#include "row_distance.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += ds_shfl_xor(v, m);
-    return v;
-}
 
 // ---- temporal average pool: [B,Hr,Wc,C] -> [B, Wc*C] -------------------------------------------
 __global__ void __launch_bounds__(256) avgpool_time_kernel(const float *x, float *pooled, int B, int Hr,
@@ -85,16 +80,7 @@ __global__ void __launch_bounds__(1024) max_abs_diff_kernel(const float *a, cons
     }
 }
 
-// ---- pairwise distance rows ------------------------------------------------------------------------
-__device__ __forceinline__ float row_sqdist(const float *a, const float *b, int D, int lane) {
-    float s = 0.f;
-    for (int k = lane; k < D; k += 64) {
-        const float d = fabsf(a[k] - b[k]);
-        s += d * d;
-    }
-    return wave_sum(s);
-}
-
+// ---- pairwise distance rows (row_sqdist: row_distance.h) --------------------------------------------
 __global__ void __launch_bounds__(256) pairwise_distance_kernel(const float *x1, const float *x2, float *d, int N,
                                                                 int D, float eps) {
     const int lane = threadIdx.x & 63;

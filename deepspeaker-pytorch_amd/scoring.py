@@ -4,10 +4,13 @@
 are embedded as `crops` fixed-length crops, the distance is taken crop-by-crop and averaged.
 `evaluate` = the threshold sweep of eval_metrics.py:5-50 (tpr / fpr / accuracy at the best-accuracy
 threshold) plus the equal error rate the reference never computes.
+`speaker_models` / `nearest` / `identify` = identification, which the reference does not have: enrolled speaker models,
+the k nearest gallery rows of every query (csrc/identify.hip) and rank-1 ... rank-k accuracy.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -86,3 +89,115 @@ def evaluate(distances: torch.Tensor, labels: torch.Tensor, thr_start: float = 0
     s = summary.cpu().numpy()
     return Verification(float(s[1]), float(s[2]), float(s[3]), thr_start + thr_step * float(s[0]), float(s[4]),
                         float(s[5]), tp, fp)
+
+
+# ---- identification: enrolled speaker models and the k nearest of them (csrc/identify.hip) ---------------------------
+MODEL_ALPHA = 10.0             # the embedding sphere's radius (model.py:181)
+NEAREST_MAX_K = 64             # DS_NEAREST_MAX_K
+NEAREST_MAX_D = 2048           # DS_NEAREST_MAX_D
+_EXCLUDE_MODES = {None: 0, "same": 1, "other": 2}
+
+
+def _host_to_dev(a: np.ndarray, dev):
+    """Host-side tables go through pinned memory, without blocking the host (as `enrolment_scores`)."""
+    t = torch.from_numpy(a)
+    return t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else t.to(dev)
+
+
+def _rows(t: torch.Tensor, name: str) -> torch.Tensor:
+    if t.dim() != 2 or t.dtype != torch.float32 or t.shape[0] < 1:
+        raise ValueError(f"{name}: expected a [rows, D] float32 tensor, got {tuple(t.shape)} {t.dtype}")
+    return t.contiguous()
+
+
+def _labels(t, n: int, name: str, dev) -> torch.Tensor:
+    t = torch.as_tensor(t)
+    if t.dim() != 1 or t.shape[0] != n or t.dtype.is_floating_point:
+        raise ValueError(f"{name}: expected {n} integer labels, got {tuple(t.shape)} {t.dtype}")
+    return t.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def speaker_models(enrol_emb: torch.Tensor, enrol_sizes, renormalise: bool = True) -> torch.Tensor:
+    """One model per enrolled speaker: the mean of the speaker's `enrol_sizes[s]` consecutive rows of `enrol_emb`,
+    with `renormalise` put back on the embeddings' sphere (L2 norm `MODEL_ALPHA`, the arithmetic of the model's own
+    normalisation).  Returns [S, D]."""
+    from .engine import L2_EPS
+    eng = _eng()
+    emb = _rows(enrol_emb, "enrol_emb")
+    sizes = np.asarray(enrol_sizes, np.int64)
+    if sizes.ndim != 1 or len(sizes) < 1 or (sizes < 1).any() or int(sizes.sum()) != emb.shape[0]:
+        raise ValueError("enrol_sizes must give one set size >= 1 per speaker, summing to the rows of enrol_emb")
+    offsets = _host_to_dev(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64), emb.device)
+    out = torch.empty((len(sizes), emb.shape[1]), dtype=torch.float32, device=emb.device)
+    eng.lib.call("ds_segment_mean_rows_f32", eng._p(emb), eng._p(offsets), eng._p(out), len(sizes), emb.shape[1],
+                 1 if renormalise else 0, MODEL_ALPHA, L2_EPS, eng._stream(emb))
+    return out
+
+
+def nearest(queries: torch.Tensor, gallery: torch.Tensor, k: int, query_labels=None, gallery_labels=None, exclude=None,
+            splits: int = 0):
+    """The `k` nearest rows of `gallery[M, D]` for every row of `queries[N, D]`: (distances [N, k] float32, indices
+    [N, k] int64), ascending, ties to the lowest index.  The candidates come from a fused f32-MFMA search that never
+    holds the N x M matrix; the reported distances are `PairwiseDistance(2)` of the pairs, bit for bit.
+    `exclude="same"` skips gallery rows that carry the query's label (its hardest negatives), `"other"` keeps only those;
+    both need the two label vectors.  Ranks that cannot be filled are index -1, distance +inf.  `splits`: gallery
+    ranges searched separately (0: chosen for the device).  Nothing is read back."""
+    eng = _eng()
+    if exclude not in _EXCLUDE_MODES:
+        raise ValueError("exclude must be None, 'same' or 'other'")
+    q, g = _rows(queries, "queries"), _rows(gallery, "gallery")
+    (n, d), m = q.shape, g.shape[0]
+    if g.shape[1] != d or g.device != q.device:
+        raise ValueError(f"queries {tuple(q.shape)} and gallery {tuple(g.shape)} must share D and the device")
+    if d % 4 != 0 or d > NEAREST_MAX_D:
+        raise ValueError(f"D = {d}: the search takes multiples of 4 up to {NEAREST_MAX_D}")
+    if not isinstance(k, int) or not 1 <= k <= NEAREST_MAX_K:
+        raise ValueError(f"k = {k!r}: expected an integer in 1..{NEAREST_MAX_K}")
+    if not isinstance(splits, int) or splits < 0:
+        raise ValueError(f"splits = {splits!r}: expected an integer >= 0")
+    mode = _EXCLUDE_MODES[exclude]
+    ql = gl = None
+    if mode:
+        if query_labels is None or gallery_labels is None:
+            raise ValueError("exclude needs query_labels and gallery_labels")
+        ql, gl = _labels(query_labels, n, "query_labels", q.device), _labels(gallery_labels, m, "gallery_labels", q.device)
+    nbytes = int(eng.lib.raw("ds_nearest_workspace_bytes")(n, m, d, k, splits))
+    if nbytes < 0:
+        raise ValueError(f"nearest: unsupported shape N={n} M={m} D={d} k={k}")
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=q.device)
+    scr_d = torch.empty((n, k), dtype=torch.float32, device=q.device)
+    scr_i = torch.empty((n, k), dtype=torch.int64, device=q.device)
+    eng.lib.call("ds_nearest_topk_f32", eng._p(q), eng._p(g), eng._p(ql), eng._p(gl), mode, eng._p(ws), eng._p(scr_d),
+                 eng._p(scr_i), n, m, d, k, splits, eng._stream(q))
+    dist = torch.empty_like(scr_d)
+    idx = torch.empty_like(scr_i)
+    eng.lib.call("ds_nearest_rescore_f32", eng._p(q), eng._p(g), eng._p(scr_i), eng._p(dist), eng._p(idx), n, m, d, k,
+                 eng._stream(q))
+    return dist, idx
+
+
+@dataclass
+class Identification:
+    labels: torch.Tensor                 # [N, k] label of the r-th nearest model (-1 where there is none)
+    distances: torch.Tensor              # [N, k]
+    indices: torch.Tensor                # [N, k] rows of `models`
+    hits: Optional[torch.Tensor] = None  # [k] int32 on the device: queries whose own label is among the first r + 1
+    rank1: Optional[float] = None
+    rank_k: Optional[float] = None
+
+
+def identify(test_emb: torch.Tensor, models: torch.Tensor, model_labels, test_labels=None, k: int = 5) -> Identification:
+    """Closed-set identification: the `k` nearest speaker models of every test embedding and, with `test_labels`, the
+    cumulative match counts `hits[r]` (rank-1 ... rank-k accuracy = hits / N; the k counts are the only read-back)."""
+    eng = _eng()
+    dist, idx = nearest(test_emb, models, k)
+    n, dev = idx.shape[0], idx.device
+    ml = _labels(model_labels, models.shape[0], "model_labels", dev)
+    labels = torch.where(idx >= 0, ml[idx.clamp_min(0)], torch.full_like(idx, -1))
+    if test_labels is None:
+        return Identification(labels, dist, idx)
+    tl = _labels(test_labels, n, "test_labels", dev)
+    hits = torch.empty(k, dtype=torch.int32, device=dev)
+    eng.lib.call("ds_rank_hits_i32", eng._p(idx), eng._p(ml), eng._p(tl), eng._p(hits), n, k, eng._stream(idx))
+    h = hits.cpu().numpy()
+    return Identification(labels, dist, idx, hits, float(h[0]) / n, float(h[k - 1]) / n)

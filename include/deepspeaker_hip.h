@@ -86,7 +86,8 @@ int ds_version(void);            /* 100: round 1; 200: round 2 (fp16 path, group
                                     300 / 301: round 3 (persistent fp16 kernels, split grouped BatchNorm backward; + ds_conv_dgrad_bnbwd_bf16);
                                     400: round 4 (fp16 training step: ds_*_f16 train entry points, ds_wgrad_f16, probes of the
                                     near-tie refinement, launch-bound timing); 500: round 5; 600: round 6 (caller-owned
-                                    scheduler workspace); 700: log-mel filterbank front end (ds_fbank_*) */
+                                    scheduler workspace); 700: log-mel filterbank front end (ds_fbank_*); 800: speaker identification
+                                    (ds_nearest_*, ds_segment_mean_rows_f32, ds_rank_hits_i32) */
 /* launch timing without marker packets: the next MFMA convolution / filter-gradient launch of the calling thread
  * records its own execution into the armed pair (hipExtLaunchKernelGGL); ds_launch_timing_end() disarms and returns
  * how many such launches happened since arming (1 = the timed call was a single kernel) */
@@ -508,6 +509,37 @@ int ds_avgpool_time_masked_f32(const float *x, const int *lens, float *pooled, i
 /* out[i] = mean of x[offsets[i] .. offsets[i+1]): enrolment sets of different sizes (train_triplet.py:350 takes the
  * mean of a trial's distances) */
 int ds_segment_mean_f32(const float *x, const long long *offsets, float *out, int n_seg, void *stream);
+
+/* ---- speaker identification (csrc/identify.hip): enrolled speaker models and a fused top-k search ----
+ * ds_nearest_topk_f32: for each of queries[N,D] the k gallery[M,D] rows (row-major f32, 16-byte aligned) with the
+ *   smallest SCREENING distance s = (|q|^2 + |g|^2) - 2 q.g, q.g from the f32 MFMA; the N x M matrix is never written.
+ *   Rows are ordered by (s, gallery index): ties go to the lowest index, and the bits of s for a pair depend on the pair
+ *   alone -- not on its tile, on `splits` or on the other rows.  out_dist / out_index [N,k] (s and int64 row numbers,
+ *   ascending); ranks that cannot be filled (fewer than k eligible rows) are (+inf, -1).
+ *   mode 0: every gallery row is eligible (the labels may be NULL); 1: rows whose label equals the query's are skipped
+ *   (hardest negatives); 2: only those rows.  query_label[N], gallery_label[M] int64.
+ *   splits: gallery ranges searched by separate workgroups and folded afterwards; 0 = chosen from the CU count.
+ *   1 <= k <= DS_NEAREST_MAX_K, D % 4 == 0 and D <= DS_NEAREST_MAX_D, else DS_ERR_BAD_SHAPE.
+ *   workspace: ds_nearest_workspace_bytes(N, M, D, k, splits) bytes (row norms + the splits' lists), 16-byte aligned.
+ * ds_nearest_rescore_f32: the distance of every (query, index[n,r]) pair again, bit-identical to
+ *   ds_pairwise_distance_f32 of the two rows (direct differences, eps = 1e-4 / D inside the root), and each query's k
+ *   entries in ascending (distance, index) order; (-1) entries stay last as (+inf, -1).  Not in place.
+ * ds_segment_mean_rows_f32: models[s,:] = mean of emb[offsets[s] .. offsets[s+1]) (rows added in order, f32);
+ *   renorm != 0: then (m / sqrt(sum m^2 + eps)) * alpha, the arithmetic of ds_l2norm_scale_f32.
+ * ds_rank_hits_i32: hits[r] = number of queries n whose query_label[n] equals gallery_label[index[n,r']] for some
+ *   r' <= r (index < 0 never matches): rank-(r+1) identification counts, reduced in a fixed order. */
+#define DS_NEAREST_MAX_K 64
+#define DS_NEAREST_MAX_D 2048
+long long ds_nearest_workspace_bytes(int N, int M, int D, int k, int splits);
+int ds_nearest_topk_f32(const float *queries, const float *gallery, const long long *query_label,
+                        const long long *gallery_label, int mode, void *workspace, float *out_dist,
+                        long long *out_index, int N, int M, int D, int k, int splits, void *stream);
+int ds_nearest_rescore_f32(const float *queries, const float *gallery, const long long *index, float *out_dist,
+                           long long *out_index, int N, int M, int D, int k, void *stream);
+int ds_segment_mean_rows_f32(const float *emb, const long long *offsets, float *models, int S, int D, int renorm,
+                             float alpha, float eps, void *stream);
+int ds_rank_hits_i32(const long long *index, const long long *gallery_label, const long long *query_label, int *hits,
+                     int N, int k, void *stream);
 
 /* ---- verification scoring on the device --------------------------------------
  * ds_group_mean_f32: score of a trial = mean over G crop-pair distances (train_triplet.py:347-350).
