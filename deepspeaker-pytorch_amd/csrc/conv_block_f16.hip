@@ -9,11 +9,12 @@
 // rows recomputed) goes from the accumulators straight into LDS in the pixel-record layout the second convolution
 // reads its fragments from -- it never exists in HBM.  Arithmetic, rounding points (the intermediate is rounded to fp16
 // exactly as the unfused path stores it) and accumulation order are those of two ds_conv_fwd_f16 calls: results are
-// bit-identical (asserted by the tests).
+// bit-identical (asserted by the tests); what the two kernels must agree on for that is shared: conv_mfma_f16_parts.h.
 #include <ds_device.h>
 #include <algorithm>
 #include <type_traits>
 #include "ds_common.h"
+#include "conv_mfma_f16_parts.h"
 
 namespace {
 
@@ -86,7 +87,8 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_block3
     constexpr int UL = (NIT + SPU - 1) / SPU;
     constexpr int SPUB = NMFB / 2 - NSUB;                       // spare slots per unit, second convolution
     constexpr int ROWS_A = BK_R + 2, ROWS_IN = BK_R + 4;
-    constexpr int TP = NSUB * 32 + 4, LPP = NSUB * 4, PPI = 64 / LPP, NRI = 32 / PPI;
+    using EG = ds_f16_epi<NSUB>;
+    constexpr int TP = EG::TP, LPP = EG::LPP, PPI = EG::PPI, NRI = EG::NRI;
     constexpr int NRES = MSB * NRI, ULR = (NRES + SPUB - 1) / SPUB;     // residual loads / the units that carry them
     static_assert(WM == 1 || WM == 2, "map width 16 or 32");
     static_assert(2 * UL <= NU && ULR + 2 <= NU && NU % RU == 0, "not enough units for the staging traffic");
@@ -103,10 +105,10 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_block3
     constexpr int RSB = C * 2 + 16;                                  // bytes per intermediate record
     constexpr int n_chunks = C / BK_CK;
     const int n_base = wn * NSUB * 32;
-    size_t lane_w = ((size_t)(n_base + l31) * 16 + 8 * lhi);
+    size_t lane_w = ds_f16_lane_w(n_base, l31, lhi);
     const size_t w_kc_stride = (size_t)NT * C * 16, w_tap_stride = (size_t)C * 16;
-    auto w_unit = [&](const _Float16 *w, int chunk, int u) {         // k-step-major units, as conv_mfma_f16_kernel
-        return w + lane_w + (size_t)(2 * chunk + (u / NT)) * w_kc_stride + (size_t)(u % NT) * w_tap_stride;
+    auto w_unit = [&](const _Float16 *w, int chunk, int u) {
+        return ds_f16_w_unit<NT, BK_CK / 16>(w, lane_w, w_kc_stride, w_tap_stride, chunk, u);
     };
 
     // ---- which tiles this workgroup walks ----
@@ -147,10 +149,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_block3
             l_off[it] = (vr * pitch + c + 1) * BK_PS + q * 16;
         }
     }
-    // lane -> pixel permutation inside a 32-pixel sub-tile (conflict-free ds_read_b128 service groups, see
-    // conv_mfma_f16_kernel.h)
-    const int lpix = (l31 < 4 || l31 >= 28) ? l31
-                   : (l31 < 12) ? l31 + 12 : (l31 < 16) ? l31 - 8 : (l31 < 20) ? l31 + 8 : l31 - 12;
+    const int lpix = ds_mfma_lpix(l31);
     int a_off[MSA];                         // first convolution: top-left record of the pixel's 3x3 window
 #pragma unroll
     for (int ms = 0; ms < MSA; ++ms) {
@@ -326,8 +325,8 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_block3
                             const ds_f32x2 sc2 = {sca[ns][g][2 * j2], sca[ns][g][2 * j2 + 1]};
                             const ds_f32x2 sh2 = {sha[ns][g][2 * j2], sha[ns][g][2 * j2 + 1]};
                             ds_f32x2 t = v * sc2 + sh2;          // (contracted to one fma per channel, like the scalar form)
-                            t[0] = fminf(fmaxf(t[0], 0.0f), 20.0f);
-                            t[1] = fminf(fmaxf(t[1], 0.0f), 20.0f);
+                            t[0] = fminf(fmaxf(t[0], DS_F16_CLIP_LO), DS_F16_CLIP_HI);
+                            t[1] = fminf(fmaxf(t[1], DS_F16_CLIP_LO), DS_F16_CLIP_HI);
                             hb[j2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t, ds_f16x2)) & keep;
                         }
                         *(ds_u32x2 *)(rec + (n_base + ns * 32 + 8 * g + 4 * lhi) * 2) = hb;
@@ -448,18 +447,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_block3
         const f32x4 sc[2] = {*(const f32x4 *)(p.sb + col), *(const f32x4 *)(p.sb + col + 4)};
         const f32x4 sh[2] = {*(const f32x4 *)(p.hb + col), *(const f32x4 *)(p.hb + col + 4)};
 #endif
-        auto put_tile = [&](int ms) {
-            float *dst = tb + (ms & 1) * (32 * TP);
-#pragma unroll
-            for (int ns = 0; ns < NSUB; ++ns)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = acc[ms][ns][4 * g + j];
-                    *(f32x4 *)(dst + lpix * TP + ns * 32 + 8 * g + 4 * lhi) = v;
-                }
-        };
+        auto put_tile = [&](int ms) { ds_f16_put_tile<NSUB>(tb + (ms & 1) * (32 * TP), acc[ms], lpix, lhi); };
         // element offset of (pixel, first channel) = pixel * y_mul + y_add: channels-last, or 16-channel planes
         const unsigned y_mul = p.y_plane_stride ? 16u : (unsigned)C;
         const unsigned y_add = p.y_plane_stride ? (unsigned)(col >> 4) * p.y_plane_stride + (unsigned)(col & 15) : (unsigned)col;
@@ -482,7 +470,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_block3
                 for (int k = 0; k < NRI; ++k) {
                     const f16x8 r8 = __builtin_bit_cast(f16x8, resv[ms][k]);
                     const int m = (wm * MSB + ms) * 32 + k * PPI + my_p;
-                    const float keep = (!MASKED || m < lin_kept) ? 20.0f : 0.0f;     // MASKED rows past the extent: clip to [0, 0]
+                    const float keep = (!MASKED || m < lin_kept) ? DS_F16_CLIP_HI : DS_F16_CLIP_LO;     // MASKED rows past the extent: clip to [0, 0]
                     f32x4 o[2];
 #pragma unroll
                     for (int hq = 0; hq < 2; ++hq)
@@ -494,8 +482,8 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_block3
                             const ds_f16x2 rh = {r8[4 * hq + 2 * j2], r8[4 * hq + 2 * j2 + 1]};
                             ds_f32x2 t = v * s2 + h2;
                             t = t + __builtin_convertvector(rh, ds_f32x2);
-                            o[hq][2 * j2] = fminf(fmaxf(t[0], 0.0f), keep);
-                            o[hq][2 * j2 + 1] = fminf(fmaxf(t[1], 0.0f), keep);
+                            o[hq][2 * j2] = fminf(fmaxf(t[0], DS_F16_CLIP_LO), keep);
+                            o[hq][2 * j2 + 1] = fminf(fmaxf(t[1], DS_F16_CLIP_LO), keep);
                         }
                     const unsigned vo = m < lin_valid ? (unsigned)(lin_base + m) * y_mul + y_add : DS_BUFFER_OOB;
                     if constexpr (OUT32) {
@@ -535,7 +523,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_block3
 static size_t block_lds_bytes(int W, int C, int waves) {
     const size_t tileA = (size_t)(BK_R + 4) * (W + 2) * BK_PS;
     const size_t interm = (size_t)(BK_R + 2) * (W + 2) * (C * 2 + 16);
-    const size_t epi = (size_t)2 * waves * 32 * (2 * 32 + 4) * 4;
+    const size_t epi = (size_t)2 * waves * 32 * ds_f16_epi<2>::TP * 4;
     return std::max(std::max(2 * tileA, interm), epi) + 64;
 }
 

@@ -5,6 +5,7 @@
 #pragma once
 #include <ds_device.h>
 #include "ds_common.h"
+#include "conv_mfma_f16_parts.h"      // ds_mfma_lpix
 
 
 constexpr int CKB = 16;             // input channels per chunk = K of one bf16 MFMA
@@ -204,11 +205,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_mfma_bf16_kernel(const Conv
         }
         out_off[m] = off;
     }
-    // Which pixel of its 32-pixel sub-tile a lane owns is free (the epilogue un-permutes): it is chosen so
-    // that the two 16-lane SERVICE GROUPS of a ds_read_b128 -- lanes {0-3,12-15,20-27} and {4-11,16-19,
-    // 28-31} -- each read 16 CONSECUTIVE pixels, i.e. consecutive 48-byte records that walk all 64 banks.
-    const int lpix = (l31 < 4 || l31 >= 28) ? l31
-                   : (l31 < 12) ? l31 + 12 : (l31 < 16) ? l31 - 8 : (l31 < 20) ? l31 + 8 : l31 - 12;
+    const int lpix = ds_mfma_lpix(l31);        // conflict-free service groups of the fragment reads
     int a_off[MSUB];                                           // byte offset of this lane's fragment
 #pragma unroll
     for (int ms = 0; ms < MSUB; ++ms) {

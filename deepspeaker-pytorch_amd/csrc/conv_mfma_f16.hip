@@ -85,8 +85,7 @@ __global__ void __launch_bounds__(256) conv_f16_splitk_reduce_kernel(const float
                                                                      const float *scale, const float *shift,
                                                                      const _Float16 *res, void *y, long long n8, int Cout,
                                                                      int flags) {
-    const float clip_lo = (flags & DS_EPI_CLIP) ? 0.0f : -__builtin_inff();
-    const float clip_hi = (flags & DS_EPI_CLIP) ? 20.0f : __builtin_inff();
+    const float clip_lo = ds_f16_clip_lo(flags), clip_hi = ds_f16_clip_hi(flags);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
         const long long e = i * 8;
         const int c = (int)(e % Cout);
@@ -129,8 +128,7 @@ static double frag_read_cost(int MT, int NI, int RT, int Wc, int IS, int row_byt
             int cnt[16] = {0}, offs[16];
             int worst = 0;
             for (int j = 0; j < 16; ++j) {
-                int m = m0 + 16 * g + j;
-                if (m >= NI * pix_per_seg) m &= ~15;    // past the last segment: the group's first pixel (kernel: a_off)
+                const int m = ds_f16_frag_pixel(m0 + 16 * g + j, NI * pix_per_seg);     // as the kernels' a_off
                 const int seg = m / pix_per_seg, rem = m % pix_per_seg;
                 const int r = rem / Wc, c = rem % Wc;
                 const int off = offs[j] = (seg < NI) ? seg * seg_bytes + (IS * r) * row_bytes + c * PSH : 0;
@@ -182,26 +180,14 @@ static void choose_strides(ConvKH &k, int MT, int PSH) {
     k.seg_pix = k.rows_in * k.pitch;
 }
 
-struct TileCfgH { int MT, NTILE, WM, NTHR; };
-constexpr int kNumCfgH = 7;
-constexpr TileCfgH kCfgH[kNumCfgH] = {
-    {160, 128, 1, 128},     // <KS,5,2,1,2>: two waves, 160x64 register tile each
-    {160, 256, 1, 256},     // <KS,5,2,1,4>
-    {320, 128, 2, 256},     // <KS,5,2,2,2>
-    {320, 64, 2, 128},      // <KS,5,2,2,1>: the 2-wave shape for 64-channel layers
-    {128, 128, 1, 128},     // <KS,4,2,1,2>: 128x64 register tiles where 160-row tiles quantise badly
-    {128, 256, 1, 256},     // <KS,4,2,1,4>
-    {640, 64, 4, 256},      // <KS,5,2,4,1>: four waves on a 64-channel layer
-};
-constexpr size_t kLdsTotal = 160 * 1024;     // per CU
-
-static size_t epi_bytes(const TileCfgH &cf) {
-    const int waves = cf.NTHR / 64, nsub = cf.NTILE / (waves / cf.WM) / 32;
-    return (size_t)2 * waves * 32 * (nsub * 32 + 4) * 4;
+// The tile configurations are the rows of kCfgH (conv_mfma_f16_kernel.h).
+// LDS of a launch: the pixel tile(s), which the epilogue's buffers reuse, then the out_off [MT] and seg_lo / seg_cnt [NI]
+// tables of the one-tile kernel and the word tile indices are passed through
+static size_t plan_lds_bytes(const TileCfgH &cf, size_t tile_bytes, int db, int NI) {
+    return std::max(tile_bytes * (db ? 2 : 1), cf.epi_bytes()) + (size_t)cf.MT() * 4 + (size_t)NI * 8 + 16;
 }
 
-// One wave per SIMD is the design point (the register tile takes most of the 512 VGPRs): a CU holds
-// 256 / NTHR workgroups, each with an equal share of the LDS.
+// The tile search: every launch runs it (resolve_f16), at most twice.
 static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, bool force_c16 = false) {
     DS_REQUIRE(s != nullptr, DS_ERR_NULL);
     DS_REQUIRE(s->B > 0 && s->H > 0 && s->W > 0 && s->Cin > 0 && s->Cout > 0, DS_ERR_BAD_SHAPE);
@@ -220,10 +206,10 @@ static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, boo
     int bc = -1, brt = 0, bni = 0, bdb = 0, bck = 32;
     for (int c = 0; c < kNumCfgH; ++c) {
         const TileCfgH &cf = kCfgH[c];
-        if (s->Cout % cf.NTILE) continue;
+        if (cf.persistent_only || s->Cout % cf.NTILE()) continue;
         if (g_forced_cfg >= 0 && c != g_forced_cfg) continue;
-        const int wg_per_cu = 256 / cf.NTHR;
-        const size_t lds_cap = kLdsTotal / wg_per_cu - 64;
+        const int wg_per_cu = cf.wg_per_cu();
+        const size_t lds_cap = cf.lds_cap();
         // (two tiles of 32 channels) > (two tiles of 16 channels: 5x5 stride-2 layers, whose input tile is 4x the
         // output tile) > (one tile of 32 channels: two barriers and exposed LDS writes per chunk)
         for (int mode = allow_db ? 0 : 2; mode < 3; ++mode) {
@@ -231,24 +217,24 @@ static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, boo
             if (mode == 1 && s->KS != 5) continue;
             if (force_c16 && s->KS == 5 && mode != 1) continue;
             const int PSH = ds_f16_record_bytes(ck);
-            const long long item_cap = (db ? 16 : 32) * cf.NTHR;
+            const long long item_cap = (db ? 16 : 32) * cf.NTHR();
             for (int rt = 1; rt <= Ho; ++rt) {
-                if ((long long)rt * Wo > cf.MT) break;
+                if ((long long)rt * Wo > cf.MT()) break;
                 const int segs_per_img = ds_ceil_div(Ho, rt);
                 const long long n_segs = (long long)s->B * segs_per_img;
-                int ni = cf.MT / (rt * Wo);
+                int ni = cf.MT() / (rt * Wo);
                 if (ni > n_segs) ni = (int)n_segs;
                 const int rows_in = IS * (rt - 1) + s->KS, cols_in = IS * (Wo - 1) + s->KS;
                 auto lds_of = [&](int n) {
                     const size_t tp = (size_t)n * rows_in * (cols_in + 4);
-                    return std::max((tp * PSH + (size_t)n * 256) * (db ? 2 : 1), epi_bytes(cf)) + (size_t)cf.MT * 4 + (size_t)n * 8;
+                    return std::max((tp * PSH + (size_t)n * 256) * (db ? 2 : 1), cf.epi_bytes()) + (size_t)cf.MT() * 4 + (size_t)n * 8;
                 };
                 auto items_of = [&](int n) { return (long long)n * std::min(rows_in, s->H) * s->W * (ck / 8); };
                 while (ni > 1 && (lds_of(ni) > lds_cap || items_of(ni) > item_cap)) --ni;
                 if (lds_of(ni) > lds_cap || items_of(ni) > item_cap) continue;
                 const long long n_mt = ds_ceil_div_ll(n_segs, ni);
-                double eff = (double)s->B * Ho * Wo / ((double)n_mt * cf.MT);
-                const long long blocks = n_mt * (s->Cout / cf.NTILE), slots = 256ll * wg_per_cu;
+                double eff = (double)s->B * Ho * Wo / ((double)n_mt * cf.MT());
+                const long long blocks = n_mt * (s->Cout / cf.NTILE()), slots = 256ll * wg_per_cu;
                 if (blocks <= slots) eff *= (double)blocks / (double)(ds_ceil_div_ll(blocks, 256) * 256);
                 else eff *= (double)blocks / (double)(ds_ceil_div_ll(blocks, slots) * slots);
                 if (mode == 1) eff *= 0.97;
@@ -260,7 +246,7 @@ static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, boo
                 // layer, the two-wave 320 x 64 one 157: the wider n tile first, whatever the M tile)
                 // 128-pixel tiles: the two-wave plan first for a 3x3 (widen_persistent turns it into the NSUB = 4 tile where
                 // Cout allows: 137.4 against 138.5 us), the four-wave one for a 5x5 (190 against 270 us)
-                static const int pref3[kNumCfgH] = {3, 6, 5, 1, 4, 2, 0}, pref5[kNumCfgH] = {3, 6, 5, 1, 2, 4, 0};
+                static const int pref3[kNumCfgH] = {3, 6, 5, 1, 4, 2, 0, 0}, pref5[kNumCfgH] = {3, 6, 5, 1, 2, 4, 0, 0};
                 eff += 1e-9 * rt + 1e-6 * (s->KS == 3 ? pref3 : pref5)[c];
                 if (eff > best) { best = eff; bc = c; brt = rt; bni = ni; bdb = db; bck = ck; }
             }
@@ -278,16 +264,16 @@ static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, boo
     k.rows_in = IS * (brt - 1) + s->KS;
     k.cols_in = IS * (Wo - 1) + s->KS;
     k.half = (k.cols_in + 1) / 2;
-    choose_strides(k, cf.MT, ds_f16_record_bytes(bck));
-    k.n_ntiles = s->Cout / cf.NTILE;
+    choose_strides(k, cf.MT(), ds_f16_record_bytes(bck));
+    k.n_ntiles = s->Cout / cf.NTILE();
     pl.cfg = bc;
     pl.db = bdb;
     pl.ck = bck;
     pl.n_mtiles = ds_ceil_div(k.n_segs, bni);
     pl.grid = pl.n_mtiles * k.n_ntiles;
     const size_t tile_bytes = (size_t)k.NI * k.seg_bytes;
-    pl.lds_bytes = std::max(tile_bytes * (bdb ? 2 : 1), epi_bytes(cf)) + (size_t)cf.MT * 4 + (size_t)k.NI * 8 + 16;
-    pl.nit = ds_ceil_div(k.NI * std::min(k.rows_in, s->H) * s->W * (bck / 8), cf.NTHR);
+    pl.lds_bytes = plan_lds_bytes(cf, tile_bytes, bdb, k.NI);
+    pl.nit = ds_ceil_div(k.NI * std::min(k.rows_in, s->H) * s->W * (bck / 8), cf.NTHR());
     return DS_OK;
 }
 
@@ -303,50 +289,115 @@ static bool plan_persistent(PlanH &pl, const ds_conv_shape *s) {
         const int lo = k.dh_min < 0 ? -k.dh_min : 0, hi = std::min(k.H - k.dh_min, k.rows_in);
         e_rows = hi > lo ? hi - lo : 1;
     }
-    const int nit_p = ds_ceil_div(k.NI * e_rows * s->W * (pl.ck / 8), cf.NTHR);
+    const int nit_p = ds_ceil_div(k.NI * e_rows * s->W * (pl.ck / 8), cf.NTHR());
     // more than 8 items per thread: only as a row block whose width divides the pixels a pass of the workgroup covers
     // (the kernel then derives every item's offsets from the first one's: LIN in conv_mfma_f16_pkernel.h)
-    const int pix_per_pass = cf.NTHR / (pl.ck / 8);
+    const int pix_per_pass = cf.NTHR() / (pl.ck / 8);
     const int lin = k.NI == 1 && pix_per_pass % s->W == 0;
     if (nit_p > 16 || (nit_p > 8 && !lin)) return false;
     pl.lin = lin;
     pl.nit = nit_p;
-    const int resident = (256 / cf.NTHR) * ds_cu_count();        // one wave per SIMD
+    const int resident = cf.wg_per_cu() * ds_cu_count();          // one wave per SIMD
     if (pl.grid > resident) pl.grid = resident;
     return true;
 }
 
-// cfg 7 exists in the persistent kernel only: the 128x128 two-wave plan (cfg 4) of a 3x3 layer with 32-channel chunks
-// and Cout % 256 == 0 widened to 128 x 256 -- each wave a 128 x 128 register tile (NSUB = 4), so that every pixel
+// kCfgWide exists in the persistent kernel only: the 128x128 two-wave plan (kCfgWideBase) of a 3x3 layer with 32-channel
+// chunks and Cout % 256 == 0 widened to 128 x 256 -- each wave a 128 x 128 register tile (NSUB = 4), so that every pixel
 // fragment read from LDS feeds four MFMAs instead of two (tools/mfma_lds_ratio.hip: the MFMA + LDS ceiling of that ratio
 // is 1.58 - 1.65 PFLOP/s against 1.35 - 1.49).  Same M tiling, same staging, same per-pixel accumulation order: results
-// are bit-identical to cfg 4.  `k.tiles` / `pl.grid` are recomputed for the halved number of N tiles.
-constexpr int kCfgWide = 7;
+// are bit-identical to the base tile.  `k.tiles` / `pl.grid` are recomputed for the halved number of N tiles.
 static bool widen_persistent(PlanH &pl, const ds_conv_shape *s) {
-    if (pl.cfg != 4 || s->KS != 3 || pl.ck != 32 || s->Cout % 256 != 0 || !pl.db) return false;
-    const size_t tile_bytes = (size_t)pl.k.NI * pl.k.seg_bytes;
-    const size_t epi = (size_t)2 * 2 * 32 * (2 * 32 + 4) * 4;           // two waves, two 32 x 68-float buffers each
-    const size_t lds = std::max(tile_bytes * 2, epi) + (size_t)128 * 4 + (size_t)pl.k.NI * 8 + 16;
-    if (lds > kLdsTotal / 2 - 64) return false;
+    const TileCfgH &wide = kCfgH[kCfgWide];
+    if (pl.cfg != kCfgWideBase || s->KS != 3 || pl.ck != 32 || s->Cout % wide.NTILE() != 0 || !pl.db) return false;
+    const size_t lds = plan_lds_bytes(wide, (size_t)pl.k.NI * pl.k.seg_bytes, 1, pl.k.NI);
+    if (lds > wide.lds_cap()) return false;
     pl.cfg = kCfgWide;
-    pl.k.n_ntiles = s->Cout / 256;
+    pl.k.n_ntiles = s->Cout / wide.NTILE();
     pl.lds_bytes = lds;
     pl.grid = pl.n_mtiles * pl.k.n_ntiles;
-    const int resident = 2 * ds_cu_count();
+    const int resident = wide.wg_per_cu() * ds_cu_count();
     pl.k.tiles = pl.grid;
     if (pl.grid > resident) pl.grid = resident;
     return true;
 }
 
+// How many ways a small launch splits its contraction: enough workgroups for two per CU, at least one chunk each
+static int splitk_ways(const PlanH &pl, const ds_conv_shape *s) {
+    const int n_chunks = s->Cin / pl.ck;
+    int ways = 1;
+    if (pl.grid > 48) return 1;                  // (measured: from ~64 workgroups on, the partial-sum traffic costs more than it saves)
+    while (ways * 2 <= 8 && ways * 2 <= n_chunks && (long long)pl.grid * ways * 2 <= 256) ways *= 2;
+    return ways;
+}
+
+// What a resolution is asked for besides the launch flags.
+//   kResolveNoChunkSwitch: ds_conv_f16_splitk_workspace_bytes sizes the workspace from the plan BEFORE the 5x5
+//   chunk-width switch below, as it always has.  Where the switch applies to a small launch (it does: DESIGN_LOG.md,
+//   "One plan resolution ...", e.g. 64 -> 128 channels on an 80x32 map at batch 1) the launch has twice the chunks, may
+//   compute more ways than that workspace holds and then runs one pass.  Kept as it is here -- changing it changes a
+//   summation order -- and named so that the difference is in one place.
+enum { kResolveNoChunkSwitch = 1 };
+
+// THE resolution of a launch: the tile search under the hint bits of `flags`, the 5x5 chunk-width switch, split-K over
+// a workspace of `ws_bytes` (has_workspace), the persistent kernel and its wide tile, the tile queues.  On success the
+// plan holds everything the launch needs except the pointers and byte strides (conv_fwd_f16) and everything the describe
+// entry points report.
+static int resolve_f16(PlanH &pl, const ds_conv_shape *s, int flags, bool has_workspace, long long ws_bytes, int how = 0) {
+    const bool no_persist = (flags & DS_CONV_HINT_NO_PERSIST) != 0;
+    int rc = plan_f16(pl, s, !(flags & DS_CONV_HINT_SINGLE_BUFFER),
+                      (flags & (DS_CONV_IN_PLANES16 | DS_CONV_HINT_CHUNK16)) != 0);
+    if (rc != DS_OK) return rc;
+    if (s->KS == 5 && pl.ck == 32 && !(flags & DS_CONV_HINT_SINGLE_BUFFER) && !no_persist && !(how & kResolveNoChunkSwitch)) {
+        // A 5x5 layer whose 32-channel chunks need more than 8 staging items per thread runs the persistent kernel with
+        // 16 items in flight -- past what the register file holds next to the 160 accumulators (a few are spilled and
+        // reloaded between the MFMAs).  The same layer in 16-channel chunks needs half the items: measured 187 vs
+        // 200 us on the 128 -> 256 layer of the bench (tools/f16_layer_ab.py).  Same arithmetic, same results.
+        PlanH p32 = pl, p16;
+        if (plan_persistent(p32, s) && p32.nit > 8 && plan_f16(p16, s, true, true) == DS_OK && p16.ck == 16) {
+            PlanH q = p16;
+            if (plan_persistent(q, s) && q.nit <= 8) pl = p16;
+        }
+    }
+    ConvKH &k = pl.k;
+    const long long n_out = (long long)s->B * k.Ho * k.Wo * s->Cout;
+    const int n_chunks = s->Cin / pl.ck;
+    pl.tiles1 = pl.grid;
+    pl.ways = (has_workspace && !(flags & DS_EPI_OUT_PLANES16)) ? splitk_ways(pl, s) : 1;
+    if (pl.ways > 1 && ws_bytes < (long long)pl.ways * n_out * 4) pl.ways = 1;
+    k.tiles = pl.grid;
+    k.chunks_per_split = ds_ceil_div(n_chunks, pl.ways);
+    k.n_splits = ds_ceil_div(n_chunks, k.chunks_per_split);
+    pl.grid *= k.n_splits;
+    pl.persistent = k.n_splits == 1 && !no_persist && plan_persistent(pl, s);
+    k.sched_queues = 1;
+    if (pl.persistent) {
+        if (!(flags & DS_CONV_HINT_NO_WIDE)) widen_persistent(pl, s);
+        // one tile queue per XCD where the tiles of a queue (t = 8 j + q) then all belong to one n tile
+        if (pl.grid % 8 == 0 && 8 % k.n_ntiles == 0 && !(flags & DS_CONV_HINT_ONE_QUEUE)) k.sched_queues = 8;
+    }
+    k.sched_lds = (int)pl.lds_bytes - 16;       // the LDS word tile indices are passed through (persistent kernel)
+    return DS_OK;
+}
+
 }  // namespace
 
-static int pack_f16(const float *w_oihw, void *w_f16, int Cout, int Cin, int KS, int mode, void *stream) {
-    DS_REQUIRE(w_oihw && w_f16, DS_ERR_NULL);
-    DS_REQUIRE(Cout > 0 && Cin > 0 && (KS == 3 || KS == 5), DS_ERR_BAD_SHAPE);
-    DS_REQUIRE(((mode == 0 ? Cin : Cout) % 16) == 0, DS_ERR_BAD_SHAPE);
+// one filter to pack: 0 and its element count in *n, or the error
+static int pack_job_check(const void *w_oihw, const void *out, int Cout, int Cin, int KS, int mode, long long *n) {
+    DS_REQUIRE(w_oihw && out, DS_ERR_NULL);
+    DS_REQUIRE(mode >= 0 && mode <= 2 && Cout > 0 && Cin > 0, DS_ERR_BAD_SHAPE);
+    DS_REQUIRE(KS == 3 || KS == 5, DS_ERR_UNSUPPORTED);
+    DS_REQUIRE((mode == 0 ? Cin : Cout) % 16 == 0, DS_ERR_BAD_SHAPE);
     DS_REQUIRE(mode != 2 || KS == 5, DS_ERR_UNSUPPORTED);
-    const long long n = (long long)Cout * Cin * (mode == 2 ? 36 : KS * KS);
-    long long g = (n + 255) / 256;
+    *n = (long long)Cout * Cin * (mode == 2 ? 36 : KS * KS);
+    return DS_OK;
+}
+
+static int pack_f16(const float *w_oihw, void *w_f16, int Cout, int Cin, int KS, int mode, void *stream) {
+    long long n;
+    const int rc = pack_job_check(w_oihw, w_f16, Cout, Cin, KS, mode, &n);
+    if (rc != DS_OK) return rc;
+    const long long g = (n + 255) / 256;
     DS_LAUNCH(pack_conv_weight_f16_kernel, (int)(g > 4096 ? 4096 : g), 256, 0, stream, w_oihw, (_Float16 *)w_f16, Cout,
               Cin, KS, mode);
     return ds_last_launch_error();
@@ -360,14 +411,11 @@ extern "C" int ds_pack_conv_weights_f16_batch(const ds_pack_job *jobs, int n_job
     int blocks = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const ds_pack_job &b = jobs[j];
-        DS_REQUIRE(b.w_oihw && b.out, DS_ERR_NULL);
-        DS_REQUIRE(b.mode >= 0 && b.mode <= 2 && b.Cout > 0 && b.Cin > 0, DS_ERR_BAD_SHAPE);
-        DS_REQUIRE(b.KS == 3 || b.KS == 5, DS_ERR_UNSUPPORTED);
-        DS_REQUIRE((b.mode == 0 ? b.Cin : b.Cout) % 16 == 0, DS_ERR_BAD_SHAPE);
-        DS_REQUIRE(b.mode != 2 || b.KS == 5, DS_ERR_UNSUPPORTED);
+        long long n;
+        const int rc = pack_job_check(b.w_oihw, b.out, b.Cout, b.Cin, b.KS, b.mode, &n);
+        if (rc != DS_OK) return rc;
         J.w[j] = b.w_oihw; J.out[j] = (_Float16 *)b.out;
         J.Cout[j] = b.Cout; J.Cin[j] = b.Cin; J.KS[j] = b.KS; J.mode[j] = b.mode;
-        const long long n = (long long)b.Cout * b.Cin * (b.mode == 2 ? 36 : b.KS * b.KS);
         const long long g = (n + 255) / 256;
         J.first[j] = blocks;
         blocks += (int)(g > 512 ? 512 : g);
@@ -417,25 +465,15 @@ extern "C" int ds_conv_f16_plan_describe(const ds_conv_shape *s, int *out8) {
 extern "C" int ds_conv_f16_plan_describe_hinted(const ds_conv_shape *s, int flags, int *out8) {
     DS_REQUIRE(out8 != nullptr, DS_ERR_NULL);
     PlanH pl;
-    int rc = plan_f16(pl, s, !(flags & DS_CONV_HINT_SINGLE_BUFFER),
-                      (flags & (DS_CONV_IN_PLANES16 | DS_CONV_HINT_CHUNK16)) != 0);
+    const int rc = resolve_f16(pl, s, flags, false, 0);
     if (rc != DS_OK) return rc;
-    if (s->KS == 5 && pl.ck == 32 && !(flags & (DS_CONV_HINT_SINGLE_BUFFER | DS_CONV_HINT_NO_PERSIST))) {   // as ds_conv_fwd_f16
-        PlanH p32 = pl, p16;
-        if (plan_persistent(p32, s) && p32.nit > 8 && plan_f16(p16, s, true, true) == DS_OK && p16.ck == 16) {
-            PlanH q = p16;
-            if (plan_persistent(q, s) && q.nit <= 8) pl = p16;
-        }
-    }
     const TileCfgH &cf = kCfgH[pl.cfg];
-    out8[0] = cf.MT; out8[1] = cf.NTILE; out8[2] = pl.k.RT; out8[3] = pl.k.NI;
-    const int tiles = pl.grid;                                   // out8[4]: tiles (= workgroups of the one-tile kernel)
-    const bool pers = !(flags & DS_CONV_HINT_NO_PERSIST) && plan_persistent(pl, s);
-    if (pers && !(flags & DS_CONV_HINT_NO_WIDE) && widen_persistent(pl, s)) out8[1] = 256;   // cfg 7: 128 x 256, NSUB = 4
-    out8[4] = tiles; out8[5] = (int)pl.lds_bytes; out8[6] = cf.NTHR;
+    out8[0] = cf.MT(); out8[1] = cf.NTILE(); out8[2] = pl.k.RT; out8[3] = pl.k.NI;
+    out8[4] = pl.tiles1;                                         // tiles (= workgroups of the one-tile kernel)
+    out8[5] = (int)pl.lds_bytes; out8[6] = cf.NTHR();
     // out8[7]: 10000 if the persistent kernel takes this plan (large launches; small ones may still be split-K)
     //          + 1000 if double-buffered + 100 for 16-channel chunks + staging items per thread
-    out8[7] = (pers ? 10000 : 0) + pl.db * 1000 + (pl.ck == 16 ? 100 : 0) + pl.nit;
+    out8[7] = (pl.persistent ? 10000 : 0) + pl.db * 1000 + (pl.ck == 16 ? 100 : 0) + pl.nit;
     return DS_OK;
 }
 
@@ -443,26 +481,18 @@ extern "C" int ds_conv_f16_plan_describe_hinted(const ds_conv_shape *s, int flag
 extern "C" void ds_conv_f16_set_layout_padding(int on) { g_layout_padding = on != 0; }
 // tuning hook (tools/f16_cfg_ab.py): cfg in [0, 7) = plan every fp16 convolution with that tile configuration (layers it
 // does not fit return DS_ERR_UNSUPPORTED); anything else = the planner's own choice.  Results do not depend on it.
-extern "C" void ds_conv_f16_set_forced_cfg(int cfg) { g_forced_cfg = (cfg >= 0 && cfg < kNumCfgH) ? cfg : -1; }
+extern "C" void ds_conv_f16_set_forced_cfg(int cfg) { g_forced_cfg = (cfg >= 0 && cfg < kNumCfgH && !kCfgH[cfg].persistent_only) ? cfg : -1; }
 
 // the LDS layout of the pixel tile in that plan: out4 = { records per tile row, bytes per tile row, bytes per segment,
 // 1000 x LDS cycles of a fragment read (1000 = conflict-free) }
 extern "C" int ds_conv_f16_plan_lds_layout(const ds_conv_shape *s, int flags, int *out4) {
     DS_REQUIRE(out4 != nullptr, DS_ERR_NULL);
     PlanH pl;
-    int rc = plan_f16(pl, s, !(flags & DS_CONV_HINT_SINGLE_BUFFER),
-                      (flags & (DS_CONV_IN_PLANES16 | DS_CONV_HINT_CHUNK16)) != 0);
+    const int rc = resolve_f16(pl, s, flags, false, 0);
     if (rc != DS_OK) return rc;
-    if (s->KS == 5 && pl.ck == 32 && !(flags & (DS_CONV_HINT_SINGLE_BUFFER | DS_CONV_HINT_NO_PERSIST))) {   // as ds_conv_fwd_f16
-        PlanH p32 = pl, p16;
-        if (plan_persistent(p32, s) && p32.nit > 8 && plan_f16(p16, s, true, true) == DS_OK && p16.ck == 16) {
-            PlanH q = p16;
-            if (plan_persistent(q, s) && q.nit <= 8) pl = p16;
-        }
-    }
     const ConvKH &k = pl.k;
     out4[0] = k.pitch; out4[1] = k.row_bytes; out4[2] = k.seg_bytes;
-    out4[3] = (int)(1000.0 * frag_read_cost(kCfgH[pl.cfg].MT, k.NI, k.RT, k.Wo, k.IS, k.row_bytes, k.seg_bytes,
+    out4[3] = (int)(1000.0 * frag_read_cost(kCfgH[pl.cfg].MT(), k.NI, k.RT, k.Wo, k.IS, k.row_bytes, k.seg_bytes,
                                             ds_f16_record_bytes(pl.ck)) + 0.5);
     return DS_OK;
 }
@@ -472,21 +502,11 @@ static long long *g_f16_probe = nullptr;
 extern "C" void ds_f16_set_probe(long long *buf) { g_f16_probe = buf; }
 #endif
 
-// How many ways a small launch splits its contraction: enough workgroups for two per CU, at least one chunk each
-static int splitk_ways(const PlanH &pl, const ds_conv_shape *s) {
-    const int n_chunks = s->Cin / pl.ck;
-    int ways = 1;
-    if (pl.grid > 48) return 1;                  // (measured: from ~64 workgroups on, the partial-sum traffic costs more than it saves)
-    while (ways * 2 <= 8 && ways * 2 <= n_chunks && (long long)pl.grid * ways * 2 <= 256) ways *= 2;
-    return ways;
-}
-
 extern "C" long long ds_conv_f16_splitk_workspace_bytes(const ds_conv_shape *s) {
     PlanH pl;
-    int rc = plan_f16(pl, s);
+    const int rc = resolve_f16(pl, s, 0, true, (1ll << 62), kResolveNoChunkSwitch);
     if (rc != DS_OK) return rc;
-    const int ways = splitk_ways(pl, s);
-    return ways > 1 ? (long long)ways * s->B * pl.k.Ho * pl.k.Wo * s->Cout * 4 : 0;
+    return pl.ways > 1 ? (long long)pl.ways * s->B * pl.k.Ho * pl.k.Wo * s->Cout * 4 : 0;
 }
 
 static int conv_fwd_f16(const ds_conv_shape *s, const void *x_f16, const void *w_f16, const float *scale,
@@ -502,19 +522,8 @@ static int conv_fwd_f16(const ds_conv_shape *s, const void *x_f16, const void *w
     const bool in_planes = (flags & DS_CONV_IN_PLANES16) != 0, out_planes = (flags & DS_EPI_OUT_PLANES16) != 0;
     DS_REQUIRE(!in_planes || s->KS == 5, DS_ERR_UNSUPPORTED);          // plane-major input needs 16-channel chunks
     DS_REQUIRE(!out_planes || !(flags & DS_EPI_OUT_F32), DS_ERR_UNSUPPORTED);
-    int rc = plan_f16(pl, s, !(flags & DS_CONV_HINT_SINGLE_BUFFER), in_planes || (flags & DS_CONV_HINT_CHUNK16) != 0);
+    int rc = resolve_f16(pl, s, flags, workspace != nullptr, ws_bytes);
     if (rc != DS_OK) return rc;
-    if (s->KS == 5 && pl.ck == 32 && !(flags & (DS_CONV_HINT_SINGLE_BUFFER | DS_CONV_HINT_NO_PERSIST))) {
-        // A 5x5 layer whose 32-channel chunks need more than 8 staging items per thread runs the persistent kernel with
-        // 16 items in flight -- past what the register file holds next to the 160 accumulators (a few are spilled and
-        // reloaded between the MFMAs).  The same layer in 16-channel chunks needs half the items: measured 187 vs
-        // 200 us on the 128 -> 256 layer of the bench (tools/f16_layer_ab.py).  Same arithmetic, same results.
-        PlanH p32 = pl, p16;
-        if (plan_persistent(p32, s) && p32.nit > 8 && plan_f16(p16, s, true, true) == DS_OK && p16.ck == 16) {
-            PlanH q = p16;
-            if (plan_persistent(q, s) && q.nit <= 8) pl = p16;
-        }
-    }
     DS_REQUIRE(!in_planes || pl.ck == 16, DS_ERR_UNSUPPORTED);
     ConvKH &k = pl.k;
     k.x_pix_stride = in_planes ? 16 : s->Cin;
@@ -526,26 +535,14 @@ static int conv_fwd_f16(const ds_conv_shape *s, const void *x_f16, const void *w
     const long long n_out = (long long)s->B * k.Ho * k.Wo * s->Cout;
     k.y_bytes = (unsigned)(n_out * ((flags & DS_EPI_OUT_F32) ? 4 : 2));
     k.res_bytes = (unsigned)(n_out * 2);
-    const int n_chunks = s->Cin / pl.ck;
-    int ways = (workspace && !out_planes) ? splitk_ways(pl, s) : 1;
-    if (ways > 1 && ws_bytes < (long long)ways * n_out * 4) ways = 1;
-    k.tiles = pl.grid;
-    k.chunks_per_split = ds_ceil_div(n_chunks, ways);
-    k.n_splits = ds_ceil_div(n_chunks, k.chunks_per_split);
     k.partial = (float *)workspace;
     k.partial_elems = (unsigned)n_out;
-    pl.grid *= k.n_splits;
 #ifdef DS_F16_PROBE
     k.probe = g_f16_probe;
 #endif
-    const bool persistent = k.n_splits == 1 && !(flags & DS_CONV_HINT_NO_PERSIST) && plan_persistent(pl, s);
-    if (persistent) {
-        if (!(flags & DS_CONV_HINT_NO_WIDE)) widen_persistent(pl, s);
+    if (pl.persistent) {
         k.sched = ds_sched_slot(stream);
         DS_REQUIRE(k.sched != nullptr, DS_ERR_NO_WORKSPACE);     // ds_sched_set_workspace is due
-        // one tile queue per XCD where the tiles of a queue (t = 8 j + q) then all belong to one n tile
-        k.sched_queues = (pl.grid % 8 == 0 && 8 % k.n_ntiles == 0 && !(flags & DS_CONV_HINT_ONE_QUEUE)) ? 8 : 1;
-        k.sched_lds = (int)pl.lds_bytes - 16;       // the plan's LDS size ends with tables the persistent kernel does not use
         if (s->KS == 3) ds_f16_launch_pk3(pl, stream);
         else if (pl.ck == 16) ds_f16_launch_pk5c16(pl, stream);
         else ds_f16_launch_pk5(pl, stream);

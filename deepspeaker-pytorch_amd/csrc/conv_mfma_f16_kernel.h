@@ -3,7 +3,9 @@
 // forward (reference model.py:69,73,192,197,202 + the fused BatchNorm-affine / residual / clipped-ReLU
 // epilogue, model.py:70-80,188-205).  One MFMA per product; measured 3.7e-4 from the reference on the
 // embedding (contract: 1e-3).  Included by conv_mfma_f16_k*.hip (one translation unit per kernel size x
-// buffering mode so the instantiations compile in parallel); planner and C ABI: conv_mfma_f16.hip.
+// buffering mode so the instantiations compile in parallel); planner and C ABI: conv_mfma_f16.hip.  The parts it has
+// in common with the persistent and the BasicBlock kernels (lane permutation, the fragment rule, filter addressing,
+// epilogue geometry): conv_mfma_f16_parts.h.
 //
 // Differences from the split-operand bf16 kernel (conv_mfma_bf16_kernel.h), all following from having a third
 // of the matrix work per byte moved:
@@ -16,6 +18,7 @@
 #include <ds_device.h>
 #include <type_traits>
 #include "ds_common.h"
+#include "conv_mfma_f16_parts.h"
 
 // CK input channels per chunk = CK/16 k-steps of the 32x32x16 MFMA per tap (32, or 16 where two 32-channel tiles
 // do not fit the LDS); a staged pixel record is CK halfs + 16 B pad = 80 / 48 bytes: 16 consecutive records walk
@@ -77,8 +80,55 @@ struct PlanH {
     int cfg, grid, n_mtiles, nit, db, ck;
     int lin = 0;                    // persistent kernel: staging offsets derived from the first item's (row blocks)
     size_t lds_bytes;
+    int tiles1 = 0;                 // workgroups of the one-tile-per-workgroup kernel for this tiling (before split-K)
+    int ways = 1;                   // split-K: the power of two the workspace is sized for (k.n_splits <= ways)
+    bool persistent = false;        // the persistent kernel takes this plan
     ConvKH k;
 };
+
+// THE tile configurations: a workgroup of WM x WN waves, each wave a register tile of MSUB x NSUB sub-tiles of 32 pixels x
+// 32 output channels.  The planner (conv_mfma_f16.hip) sizes its plans from the rows, launch_h / launch_p instantiate the
+// kernels from them; `cfg` everywhere is an index into this table.
+struct TileCfgH {
+    int MSUB, NSUB, WM, WN;
+    bool persistent_only;           // no instantiation of the one-tile-per-workgroup kernel; never chosen by plan_f16
+    constexpr int MT() const { return MSUB * WM * 32; }             // pixels per tile
+    constexpr int NTILE() const { return NSUB * WN * 32; }          // output channels per tile
+    constexpr int NTHR() const { return WM * WN * 64; }
+    // the epilogue's turn-around buffers: two of 32 rows per wave (64 channels at a time whatever NSUB is)
+    constexpr size_t epi_bytes() const { return (size_t)2 * WM * WN * 32 * ds_f16_epi<2>::TP * 4; }
+    // one wave per SIMD is the design point (the register tile takes most of the 512 VGPRs): a CU holds 256 / NTHR
+    // workgroups, each with an equal share of its LDS
+    constexpr int wg_per_cu() const { return 256 / NTHR(); }
+    constexpr size_t lds_cap() const { return kLdsTotal / wg_per_cu() - 64; }
+    static constexpr size_t kLdsTotal = 160 * 1024;                 // per CU
+};
+constexpr int kNumCfgH = 8;
+constexpr TileCfgH kCfgH[kNumCfgH] = {
+    {5, 2, 1, 2, false},    // 160 x 128: two waves, 160x64 register tile each
+    {5, 2, 1, 4, false},    // 160 x 256, four waves
+    {5, 2, 2, 2, false},    // 320 x 128
+    {5, 2, 2, 1, false},    // 320 x 64: the 2-wave shape for 64-channel layers
+    {4, 2, 1, 2, false},    // 128 x 128: 128x64 register tiles where 160-row tiles quantise badly
+    {4, 2, 1, 4, false},    // 128 x 256
+    {5, 2, 4, 1, false},    // 640 x 64: four waves on a 64-channel layer
+    {4, 4, 1, 2, true},     // 128 x 256, two waves, each a 128 x 128 register tile (256 accumulator registers, every LDS
+                            // fragment read feeds four MFMAs): what widen_persistent turns cfg 4 into -- 3x3 layers,
+                            // 32-channel chunks, Cout % 256 == 0 (the 512-channel layers on 10x4 maps)
+};
+constexpr int kCfgWide = 7, kCfgWideBase = 4;
+static_assert(kCfgH[kCfgWide].MT() == kCfgH[kCfgWideBase].MT() && kCfgH[kCfgWide].NTHR() == kCfgH[kCfgWideBase].NTHR() &&
+                  kCfgH[kCfgWide].NTILE() == 2 * kCfgH[kCfgWideBase].NTILE(),
+              "the wide tile is its base tile with twice the channels per wave: same M tiling, same staging");
+
+// run-time cfg -> compile-time row: f(std::integral_constant<int, cfg>)
+template <int N = 0, class F>
+static void ds_f16_with_cfg(int cfg, F &&f) {
+    if constexpr (N < kNumCfgH) {
+        if (cfg == N) f(std::integral_constant<int, N>{});
+        else ds_f16_with_cfg<N + 1>(cfg, f);
+    }
+}
 
 // one entry point per translation unit (kernel size x buffering)
 void ds_f16_launch_k3db(const PlanH &pl, void *stream);
@@ -119,7 +169,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
     const int seg0 = tile_m * p.NI;
     const int pix_per_seg = p.RT * p.Wo;
     // the pixel-tile region doubles as the epilogue's transposition buffers (two of 32 x (NSUB*32+4) floats per wave)
-    constexpr int EPI_BYTES = 2 * WM * WN * 32 * (NSUB * 32 + 4) * 4;
+    constexpr int EPI_BYTES = 2 * WM * WN * 32 * ds_f16_epi<NSUB>::TP * 4;
     const int tile_bytes = p.NI * p.seg_bytes;
     const int tiles_bytes = (DB ? 2 : 1) * tile_bytes;
     const int stage_bytes = tiles_bytes > EPI_BYTES ? tiles_bytes : EPI_BYTES;
@@ -131,15 +181,10 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
     const int c0 = split * p.chunks_per_split;                  // this workgroup's chunk range [c0, c0 + n_chunks)
     const int n_chunks = (p.Cin / CKH - c0) < p.chunks_per_split ? (p.Cin / CKH - c0) : p.chunks_per_split;
     const int n_base = tile_n * NTILE + wn * NSUB * 32;
-    const size_t lane_w = ((size_t)(n_base + l31) * 16 + 8 * lhi);      // in halfs
+    const size_t lane_w = ds_f16_lane_w(n_base, l31, lhi);              // in halfs
     const size_t w_kc_stride = (size_t)NT * p.Cout * 16;                // one 16-channel slab: [tap][Cout][16]
     const size_t w_tap_stride = (size_t)p.Cout * 16;
-    // unit u of a chunk = (k-step u / NT, tap u % NT): filter slab KPT*chunk + u / NT, tap u % NT.  K-step-major, so
-    // that a pixel's products are accumulated in the same order with 16- and 32-channel chunks (results do not
-    // depend on which the planner picks for a batch size).
-    auto w_unit = [&](int chunk, int u) {
-        return p.w + lane_w + (size_t)(KPT * chunk + (u / NT)) * w_kc_stride + (size_t)(u % NT) * w_tap_stride;
-    };
+    auto w_unit = [&](int chunk, int u) { return ds_f16_w_unit<NT, KPT>(p.w, lane_w, w_kc_stride, w_tap_stride, chunk, u); };
 
     f16x8 bq[RU][NSUB];
 #pragma unroll
@@ -234,8 +279,6 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
                 l_off[it] = CKH * 2;                // the pad bytes of pixel record 0
                 if (seg < p.NI) {
                     const int rr = lo + vr - row0;
-                    // stride-2 layers keep even tile columns in slots [0, half) and odd ones in [half, cols_in),
-                    // so that the 32 lanes of a fragment read (stride-2 columns) touch CONSECUTIVE records
                     const int cc = c - p.dw_min;
                     const int pc = (p.IS == 2) ? ((cc & 1) ? p.half + (cc >> 1) : (cc >> 1)) : cc;
                     g_off[it] = ((img_row + rr) * p.W + c) * p.x_pix_stride + q * 8;
@@ -285,18 +328,11 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
         }
     }
     DS_F16_STAMP(7);
-    // Which pixel of its 32-pixel sub-tile a lane owns is free (the epilogue un-permutes): it is chosen so
-    // that the two 16-lane SERVICE GROUPS of a ds_read_b128 -- lanes {0-3,12-15,20-27} and {4-11,16-19,
-    // 28-31} -- each read 16 CONSECUTIVE pixels, i.e. consecutive 80-byte records that walk all 64 banks.
-    const int lpix = (l31 < 4 || l31 >= 28) ? l31
-                   : (l31 < 12) ? l31 + 12 : (l31 < 16) ? l31 - 8 : (l31 < 20) ? l31 + 8 : l31 - 12;
+    const int lpix = ds_mfma_lpix(l31);
     int a_off[MSUB];                                           // byte offset of this lane's fragment
 #pragma unroll
     for (int ms = 0; ms < MSUB; ++ms) {
-        // (a pixel past the tile's last segment reads what the first pixel of its 16-pixel service group reads -- the
-        // same address is served in the same LDS cycle -- or record 0 if that one is past the end as well)
-        int m = (wm * MSUB + ms) * 32 + lpix;
-        if (m >= p.NI * pix_per_seg) m &= ~15;
+        const int m = ds_f16_frag_pixel((wm * MSUB + ms) * 32 + lpix, p.NI * pix_per_seg);
         const int seg = ds_div_small(m, pix_per_seg, rcp_pps);
         const int rem = m - seg * pix_per_seg;
         const int r = ds_div_small(rem, p.Wo, rcp_wc), c = rem - r * p.Wo;
@@ -400,15 +436,10 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
     }
 
     // ---- epilogue ----
-    // The filters were the A operand of every MFMA, so the accumulators hold the TRANSPOSED product: a lane
-    // owns one output pixel (lpix of the 32-pixel sub-tile) and, per register quad g, four consecutive output
-    // channels 8g + 4*lhi .. +3.  Each 32-pixel sub-tile is turned around through a wave-private LDS buffer
-    // (the pixel tile's space, free now) so that residual loads and stores move whole pixel rows: the
-    // NSUB*32 channels of a pixel are contiguous across NSUB*4 lanes, 8 channels = 16 bytes of fp16 per lane.
-    constexpr int TP = NSUB * 32 + 4;           // buffer row pitch in floats (conflict-free 16-byte writes)
-    constexpr int LPP = NSUB * 4;               // lanes per pixel row
-    constexpr int PPI = 64 / LPP;               // pixel rows per instruction
-    constexpr int NRI = 32 / PPI;               // instructions per sub-tile
+    // Each 32-pixel sub-tile is turned around through a wave-private LDS buffer (the pixel tile's space, free now):
+    // geometry ds_f16_epi (conv_mfma_f16_parts.h).
+    using EG = ds_f16_epi<NSUB>;
+    constexpr int TP = EG::TP, LPP = EG::LPP, PPI = EG::PPI, NRI = EG::NRI;
     // a split-K workgroup stores raw f32 accumulators; the reduction kernel applies the epilogue
     const int flags = p.n_splits > 1 ? DS_EPI_OUT_F32 : p.flags;
     DS_F16_STAMP(2);
@@ -428,8 +459,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
     // Rows of a ragged tile get an out-of-range buffer offset (the store is dropped, the load returns
     // zeros) and a layer without residual reads "out of range" too: no branch around any memory instruction.
     const bool out32 = (flags & DS_EPI_OUT_F32) != 0;
-    const float clip_lo = (flags & DS_EPI_CLIP) ? 0.0f : -__builtin_inff();
-    const float clip_hi = (flags & DS_EPI_CLIP) ? 20.0f : __builtin_inff();
+    const float clip_lo = ds_f16_clip_lo(flags), clip_hi = ds_f16_clip_hi(flags);
     const ds_buffer ybuf = p.n_splits > 1 ? ds_make_buffer(p.partial + (size_t)split * p.partial_elems, p.partial_elems * 4u)
                                           : ds_make_buffer(p.y, p.y_bytes);
     const ds_buffer rbuf = ds_make_buffer((flags & DS_EPI_RESIDUAL) ? (const void *)p.res : (const void *)p.y,
@@ -455,7 +485,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
             resv[ms][k] = ds_buffer_load_f32x4(rbuf, off >= 0 ? cl * 2u : DS_BUFFER_OOB);
         }
     auto put_tile = [&](int ms) {               // accumulators of sub-tile ms -> this wave's buffer ms & 1
-        float *dst = tb + (ms & 1) * (32 * TP);
+        float *dst = tb + (ms & 1) * (32 * TP);         // (ds_f16_put_tile written out: conv_mfma_f16_parts.h says why)
 #pragma unroll
         for (int ns = 0; ns < NSUB; ++ns)
 #pragma unroll
@@ -523,13 +553,10 @@ static void launch_nit_h(const PlanH &pl, void *stream) {
 
 template <int KS, bool DB, int CK = 32>
 static void launch_h(const PlanH &pl, void *stream) {
-    if (pl.cfg == 0) launch_nit_h<KS, 5, 2, 1, 2, DB, CK>(pl, stream);          // 160x128, two waves
-    else if (pl.cfg == 1) launch_nit_h<KS, 5, 2, 1, 4, DB, CK>(pl, stream);     // 160x256, four waves
-    else if (pl.cfg == 2) launch_nit_h<KS, 5, 2, 2, 2, DB, CK>(pl, stream);     // 320x128
-    else if (pl.cfg == 3) launch_nit_h<KS, 5, 2, 2, 1, DB, CK>(pl, stream);     // 320x64, two waves
-    else if (pl.cfg == 4) launch_nit_h<KS, 4, 2, 1, 2, DB, CK>(pl, stream);     // 128x128, two waves
-    else if (pl.cfg == 5) launch_nit_h<KS, 4, 2, 1, 4, DB, CK>(pl, stream);     // 128x256
-    else launch_nit_h<KS, 5, 2, 4, 1, DB, CK>(pl, stream);                      // 640x64, four waves
+    ds_f16_with_cfg(pl.cfg, [&](auto c) {
+        constexpr TileCfgH cf = kCfgH[decltype(c)::value];
+        if constexpr (!cf.persistent_only) launch_nit_h<KS, cf.MSUB, cf.NSUB, cf.WM, cf.WN, DB, CK>(pl, stream);
+    });
 }
 
 }  // namespace

@@ -2,7 +2,8 @@
 // geometry every full-size layer of the eval forward has: a double-buffered pixel tile whose M rows are either one
 // block of rows of one image (NI == 1) or a run of whole images (segs_per_img == 1), no split-K.  Same products, same
 // accumulation order, same epilogue arithmetic: bit-identical to conv_mfma_f16_kernel (asserted by the tests); the
-// planner (conv_mfma_f16.hip) falls back to that kernel for everything else.
+// planner (conv_mfma_f16.hip) falls back to that kernel for everything else.  The parts both kernels (and the BasicBlock
+// kernel) must agree on for that are written once, in conv_mfma_f16_parts.h.
 //
 // What persistence buys (reference model.py:69,73,192,197,202 run through ds_conv_fwd_f16; measured on the
 // one-tile-per-workgroup kernel with tools/f16_phase_probe.py: 7-21 k clocks of prologue and 8-10 k of epilogue next
@@ -54,7 +55,8 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
     // buffers, the lane -> (pixel, 8 channels) assignment and the register use of a step are those of the 64-wide tiles):
     // a wave's tile is MSUB x NH steps, step e = (ms, nh) = (e / NH, e % NH), channels n_base + 64 nh ...
     constexpr int ENS = 2, NH = NSUB / ENS, NE = MSUB * NH;
-    constexpr int TP = ENS * 32 + 4, LPP = ENS * 4, PPI = 64 / LPP, NRI = 32 / PPI;
+    using EG = ds_f16_epi<ENS>;
+    constexpr int TP = EG::TP, LPP = EG::LPP, PPI = EG::PPI, NRI = EG::NRI;
     // residual rows: those of the first RPRE steps are requested in the last units of the tile's last chunk, the
     // others two steps ahead inside the epilogue (all NE * NRI of them held through the stream's tail would cost
     // up to 80 registers)
@@ -114,8 +116,6 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
             const int vr = ds_div_small(pix, p.W, rcp_w), c = pix - vr * p.W;
             const int sg = ds_div_small(vr, e_rows, rcp_er), rr = e_lo + vr - sg * e_rows;
             const int cc = c - p.dw_min;
-            // stride-2 layers keep even tile columns in slots [0, half) and odd ones in [half, cols_in), so that the
-            // 32 lanes of a fragment read (stride-2 columns) touch CONSECUTIVE records
             const int pc = (p.IS == 2) ? ((cc & 1) ? p.half + (cc >> 1) : (cc >> 1)) : cc;
             const bool ok = sg < p.NI;
             g_tab[it] = ok ? (unsigned)((((sg * p.H + rr) * p.W + c) * p.x_pix_stride + q * 8) * 2) : OOB;
@@ -136,15 +136,14 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
         const int o = l_tab[0] + it * l_step;
         return o <= last_row_l ? o : CKH * 2;
     };
-    // Which pixel of its 32-pixel sub-tile a lane owns is free (the epilogue un-permutes): chosen so that the two
-    // 16-lane SERVICE GROUPS of a ds_read_b128 each read 16 CONSECUTIVE pixels (see conv_mfma_f16_kernel.h)
+    // Which pixel of its 32-pixel sub-tile a lane owns: ds_mfma_lpix (conv_mfma_f16_parts.h) written out -- see there
     const int lpix = (l31 < 4 || l31 >= 28) ? l31
                    : (l31 < 12) ? l31 + 12 : (l31 < 16) ? l31 - 8 : (l31 < 20) ? l31 + 8 : l31 - 12;
     int a_off[MSUB];                                           // byte offset of this lane's fragment
 #pragma unroll
     for (int ms = 0; ms < MSUB; ++ms) {
-        // (a pixel past the tile's last segment reads what the first pixel of its 16-pixel service group reads -- the
-        // same address is served in the same LDS cycle -- or record 0 if that one is past the end as well)
+        // (a pixel past the tile's last segment: the rule of ds_f16_frag_pixel, conv_mfma_f16_parts.h, written out --
+        // see there for why this kernel does not call it)
         int m = (wm * MSUB + ms) * 32 + lpix;
         if (m >= p.NI * pix_per_seg) m &= ~15;
         const int seg = ds_div_small(m, pix_per_seg, rcp_pps);
@@ -169,8 +168,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
     const int my_c = (lane % LPP) * 8, my_p = lane / LPP;
     const int flags = p.flags;
     const bool out32 = (flags & DS_EPI_OUT_F32) != 0;
-    const float clip_lo = (flags & DS_EPI_CLIP) ? 0.0f : -__builtin_inff();
-    const float clip_hi = (flags & DS_EPI_CLIP) ? 20.0f : __builtin_inff();
+    const float clip_lo = ds_f16_clip_lo(flags), clip_hi = ds_f16_clip_hi(flags);
     const ds_buffer ybuf = ds_make_buffer(p.y, p.y_bytes);
     const ds_buffer rbuf = ds_make_buffer((flags & DS_EPI_RESIDUAL) ? (const void *)p.res : (const void *)p.y,
                                           (flags & DS_EPI_RESIDUAL) ? p.res_bytes : 0u);
@@ -229,11 +227,8 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
 #pragma unroll
         for (int it = 0; it < NIT; ++it) st[it] = ds_buffer_load_f32x4(xb, g_rel(it) - x_lo);
     }
-    size_t lane_w = ((size_t)(ta.tile_n * NTILE + wn * NSUB * 32 + l31) * 16 + 8 * lhi);       // in halfs
-    // unit u of a chunk = (k-step u / NT, tap u % NT): filter slab KPT*chunk + u / NT, tap u % NT (k-step-major)
-    auto w_unit = [&](size_t lw, int chunk, int u) {
-        return p.w + lw + (size_t)(KPT * chunk + (u / NT)) * w_kc_stride + (size_t)(u % NT) * w_tap_stride;
-    };
+    size_t lane_w = ds_f16_lane_w(ta.tile_n * NTILE + wn * NSUB * 32, l31, lhi);               // in halfs
+    auto w_unit = [&](size_t lw, int chunk, int u) { return ds_f16_w_unit<NT, KPT>(p.w, lw, w_kc_stride, w_tap_stride, chunk, u); };
     f16x8 bq[RU][NSUB];
     if constexpr (RING_THROUGH) {
 #pragma unroll
@@ -266,7 +261,7 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
         unsigned nb_bytes = 0, n_lo = 0;
         const bool has_next = t_next < t_end;
         if (has_next) tile_at(t_next, tn, nb_base, nb_bytes, n_lo);
-        size_t lane_wn = ((size_t)(tn.tile_n * NTILE + wn * NSUB * 32 + l31) * 16 + 8 * lhi);
+        size_t lane_wn = ds_f16_lane_w(tn.tile_n * NTILE + wn * NSUB * 32, l31, lhi);
         DS_OPAQUE_VGPR(lane_wn);
 
         if constexpr (!RING_THROUGH) {          // the ring's first RU units, per tile
@@ -415,18 +410,8 @@ __global__ void __launch_bounds__(WM * WN * 64) DS_ONE_WAVE_PER_SIMD conv_mfma_f
 #ifndef DS_EPI_TABLES_LATE          // (A/B builds, tools/f16_ab.py: the round-5 order -- prefetch first)
         if constexpr (EARLY_PREFETCH) prefetch_next();
 #endif
-        auto put_tile = [&](int e) {                // accumulators of step e -> this wave's buffer e & 1
-            float *dst = tb + (e & 1) * (32 * TP);
-            const int ms = e / NH, nh = e % NH;
-#pragma unroll
-            for (int ns = 0; ns < ENS; ++ns)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = acc[ms][ENS * nh + ns][4 * g + j];
-                    *(f32x4 *)(dst + lpix * TP + ns * 32 + 8 * g + 4 * lhi) = v;
-                }
+        auto put_tile = [&](int e) {                // accumulators of step e = (ms, nh) -> this wave's buffer e & 1
+            ds_f16_put_tile<ENS>(tb + (e & 1) * (32 * TP), &acc[e / NH][ENS * (e % NH)], lpix, lhi);
         };
         // element offset of (pixel, first channel) = pixel * y_mul + y_add: channels-last, or 16-channel planes
         const unsigned y_mul = p.y_plane_stride ? 16u : (unsigned)p.Cout;
@@ -520,19 +505,11 @@ static void launch_nit_p(const PlanH &pl, void *stream) {
 
 template <int KS, int CK = 32>
 static void launch_p(const PlanH &pl, void *stream) {
-    if (pl.cfg == 0) launch_nit_p<KS, 5, 2, 1, 2, CK>(pl, stream);          // 160x128, two waves
-    else if (pl.cfg == 1) launch_nit_p<KS, 5, 2, 1, 4, CK>(pl, stream);     // 160x256, four waves
-    else if (pl.cfg == 2) launch_nit_p<KS, 5, 2, 2, 2, CK>(pl, stream);     // 320x128
-    else if (pl.cfg == 3) launch_nit_p<KS, 5, 2, 2, 1, CK>(pl, stream);     // 320x64, two waves
-    else if (pl.cfg == 4) launch_nit_p<KS, 4, 2, 1, 2, CK>(pl, stream);     // 128x128, two waves
-    else if (pl.cfg == 5) launch_nit_p<KS, 4, 2, 1, 4, CK>(pl, stream);     // 128x256
-    else if (pl.cfg == 6) launch_nit_p<KS, 5, 2, 4, 1, CK>(pl, stream);     // 640x64, four waves
-    else {
-        // cfg 7 (persistent kernel only; the planner upgrades a cfg-4 plan of a layer with Cout % 256 == 0): 128x256,
-        // two waves, each a 128 x 128 register tile (NSUB = 4: 256 accumulator registers, every LDS fragment read feeds
-        // four MFMAs) -- the 512-channel 3x3 layers on 10x4 maps
-        if constexpr (KS == 3 && CK == 32) launch_nit_p<KS, 4, 4, 1, 2, CK>(pl, stream);
-    }
+    ds_f16_with_cfg(pl.cfg, [&](auto c) {
+        constexpr TileCfgH cf = kCfgH[decltype(c)::value];
+        // (the NSUB = 4 row is planned for 3x3 layers with 32-channel chunks only: widen_persistent)
+        if constexpr (!cf.persistent_only || (KS == 3 && CK == 32)) launch_nit_p<KS, cf.MSUB, cf.NSUB, cf.WM, cf.WN, CK>(pl, stream);
+    });
 }
 
 }  // namespace
