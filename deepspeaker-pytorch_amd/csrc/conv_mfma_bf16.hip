@@ -19,6 +19,7 @@
 #include "ds_common.h"
 
 #include "conv_mfma_bf16_kernel.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -71,6 +72,8 @@ __global__ void __launch_bounds__(256) pack_conv_weight_bf16_batch_kernel(const 
 // LDS cycles (1 = conflict-free) of one ds_read_b128 fragment read for a candidate row pitch: simulates
 // the two 16-lane service groups of lanes 0..31 (the upper half-wave behaves identically; each group
 // holds 16 consecutive pixels, see `lpix` in the kernel) over every 32-row sub-tile of the M tile.  Bank slot of a record = (record * PSB / 16) mod 16.
+// NOT the fp16 planner's function of the same name: that one serves lanes reading the same address together and maps
+// the pixels past the tile's last segment with ds_f16_frag_pixel, as its kernels do; this kernel does neither.
 static double frag_read_cost(int MT, int NI, int RT, int Wc, int IS, int rows_in, int pitch) {
     const int pix_per_seg = RT * Wc, seg_pix = rows_in * pitch;
     double total = 0.0;
@@ -94,89 +97,52 @@ static double frag_read_cost(int MT, int NI, int RT, int Wc, int IS, int rows_in
     return n ? total / n : 1.0;
 }
 
-// ---- host-side plan (same objective as the f32 planner; limits: 64 KiB LDS, 2 workgroups per CU) ----
-struct TileCfgB { int MT, NTILE, WM, wg_per_cu, NTHR; };
-constexpr int kNumCfgB = 9;
-constexpr TileCfgB kCfgB[kNumCfgB] = {
-    {128, 64, 2, 3, 256},      // <KS,2,1,2,2>
-    {160, 128, 1, 2, 256},     // <KS,5,1,1,4>
-    {256, 64, 2, 2, 256},      // <KS,4,1,2,2>
-    {160, 128, 1, 2, 128},     // <KS,5,2,1,2>: two waves, 160x64 register tile each, one wave per SIMD; up to 80 KiB LDS
-    // one workgroup per CU, four waves with a 160x64 register tile each and the whole 160 KiB of LDS: the
-    // stride-2 layers, whose input tile is 4x the output tile, keep full M tiles this way
-    {160, 256, 1, 1, 256},     // <KS,5,2,1,4>
-    {320, 128, 2, 1, 256},     // <KS,5,2,2,2>
-    {320, 64, 2, 2, 128},      // <KS,5,2,2,1>: the 2-wave shape for 64-channel layers
-    {128, 128, 1, 2, 128},     // <KS,4,2,1,2>: 128x64 register tiles where 160-row tiles quantise badly
-    {128, 256, 1, 1, 256},     // <KS,4,2,1,4>: the same with the whole LDS (three 10x4 maps of the last 5x5 layer)
-};
-constexpr size_t kLdsCapB[kNumCfgB] = {64 * 1024, 64 * 1024, 64 * 1024, 80 * 1024, 160 * 1024 - 64, 160 * 1024 - 64,
-                                       80 * 1024, 80 * 1024, 160 * 1024 - 64};
-
-// bytes of the epilogue's per-wave transposition buffers (they alias the pixel tile)
-static size_t epi_bytes(const TileCfgB &cf) {
-    const int waves = cf.NTHR / 64, nsub = cf.NTILE / (waves / cf.WM) / 32;
-    return (size_t)waves * 32 * (nsub * 32 + 4) * 4;
-}
-
-
+// ---- host-side plan: the shared tile search (conv_plan.h) over the rows of kCfgB (conv_mfma_bf16_kernel.h) ----
 static int g_forced_cfg_b = -1;      // tuning hook (tools/bf16_cfg_ab.py): plan with this tile configuration only
+
+// LDS of a launch whose pixel tile holds tile_pix records: the tile (hi + lo planes for bf16x3), which the epilogue's
+// buffers alias, then the out_off [MT], seg_lo / seg_cnt [NI] and statistics [WM][NTILE][2] tables.  The launch asks
+// for kLdsSlackB bytes more than this; the configurations' caps are compared against this figure.
+constexpr size_t kLdsSlackB = 16;
+static size_t plan_lds_bytes(const TileCfgB &cf, size_t tile_pix, bool x3, int NI) {
+    return std::max(tile_pix * PSB * (x3 ? 2 : 1), cf.epi_bytes()) + (size_t)cf.MT() * 4 + (size_t)NI * 8 + (size_t)cf.WM * cf.NTILE() * 8;
+}
 
 // `s` describes the tile grid: input [B,H,W,Cin], KS x KS taps, stride s->stride, output grid Ho x Wo computed
 // with `pad`.  The forward convolution writes that grid densely; the stride-2 data gradient runs four such
 // grids (parity classes) whose outputs interleave in y (out_* arguments).
 static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride = 1, int out_h0 = 0, int out_w0 = 0,
                      int out_H = 0, int out_W = 0, int grid_H = 0, int grid_W = 0) {
-    DS_REQUIRE(s != nullptr, DS_ERR_NULL);
-    DS_REQUIRE(s->B > 0 && s->H > 0 && s->W > 0 && s->Cin > 0 && s->Cout > 0, DS_ERR_BAD_SHAPE);
-    DS_REQUIRE(s->KS == 3 || s->KS == 5, DS_ERR_UNSUPPORTED);
-    DS_REQUIRE(s->stride == 1 || s->stride == 2, DS_ERR_UNSUPPORTED);
-    DS_REQUIRE(s->Cin % CKB == 0 && s->Cout % 64 == 0, DS_ERR_BAD_SHAPE);
+    int Ho, Wo;
+    const int rc = ds_plan_check_shape(s, CKB, false, Ho, Wo, grid_H, grid_W);
+    if (rc != DS_OK) return rc;
     const int pad = s->KS / 2;
-    const int Ho = grid_H > 0 ? grid_H : (s->H + 2 * pad - s->KS) / s->stride + 1;
-    const int Wo = grid_W > 0 ? grid_W : (s->W + 2 * pad - s->KS) / s->stride + 1;
     const int yH = out_H > 0 ? out_H : Ho, yW = out_W > 0 ? out_W : Wo;
-    DS_REQUIRE(Ho > 0 && Wo > 0 && Wo <= 128, DS_ERR_BAD_SHAPE);
-    DS_REQUIRE((long long)s->B * s->H * s->W * s->Cin < (1ll << 31), DS_ERR_BAD_SHAPE);
     DS_REQUIRE((long long)s->B * Ho < (1ll << 24), DS_ERR_BAD_SHAPE);                  // reciprocal index arithmetic
     DS_REQUIRE((long long)s->B * yH * yW * s->Cout < (1ll << 30), DS_ERR_BAD_SHAPE);   // 32-bit byte offsets
     const int IS = s->stride;
-    const bool big_tile_ok = x3;                 // the 2-wave shape is tuned for (and only built for) bf16x3
     double best = -1.0;
     int bc = -1, brt = 0, bni = 0;
     for (int c = 0; c < kNumCfgB; ++c) {
         const TileCfgB &cf = kCfgB[c];
-        if (s->Cout % cf.NTILE) continue;
-        if (c >= 3 && !big_tile_ok) continue;
+        if (s->Cout % cf.NTILE()) continue;
+        if (cf.x3_only && !x3) continue;
         if (g_forced_cfg_b >= 0 && c != g_forced_cfg_b) continue;
-        const size_t lds_cap = kLdsCapB[c];
-        const long long item_cap = c >= 3 ? 32 * cf.NTHR : 16 * cf.NTHR;
-        for (int rt = 1; rt <= Ho; ++rt) {
-            if ((long long)rt * Wo > cf.MT) break;
-            const int segs_per_img = ds_ceil_div(Ho, rt);
-            const long long n_segs = (long long)s->B * segs_per_img;
-            int ni = cf.MT / (rt * Wo);
-            if (ni > n_segs) ni = (int)n_segs;
-            const int rows_in = IS * (rt - 1) + s->KS, cols_in = IS * (Wo - 1) + s->KS;
-            // feasibility with the widest row pitch the conflict search may pick (cols_in + 4); the pitch
-            // itself is chosen once, for the winning geometry (this function runs on every launch)
-            auto lds_of = [&](int n) {
-                const size_t tp = (size_t)n * rows_in * (cols_in + 4);
-                return std::max(tp * PSB * (x3 ? 2 : 1), epi_bytes(cf)) + (size_t)cf.MT * 4 + (size_t)n * 8 + (size_t)cf.WM * cf.NTILE * 8;
-            };
-            // staged items: 4-channel quarters of the in-image pixels only
-            auto items_of = [&](int n) { return (long long)n * std::min(rows_in, s->H) * s->W * (CKB / 4); };
-            while (ni > 1 && (lds_of(ni) > lds_cap || items_of(ni) > item_cap)) --ni;
-            if (lds_of(ni) > lds_cap || items_of(ni) > item_cap) continue;
-            const long long n_mt = ds_ceil_div_ll(n_segs, ni);
-            double eff = (double)s->B * Ho * Wo / ((double)n_mt * cf.MT);
-            const long long blocks = n_mt * (s->Cout / cf.NTILE), slots = 256ll * cf.wg_per_cu;
-            if (blocks <= slots) eff *= (double)blocks / (double)(ds_ceil_div_ll(blocks, 256) * 256);
-            else eff *= (double)blocks / (double)(ds_ceil_div_ll(blocks, slots) * slots);
+        const long long item_cap = (long long)cf.items_per_thread * cf.NTHR();
+        // feasibility with the widest row pitch the conflict search may pick (cols_in + 4); the pitch itself is chosen
+        // once, for the winning geometry (this function runs on every launch).  Staged items: 4-channel quarters of
+        // the in-image pixels only
+        auto fits = [&](int n, int rows_in, int cols_in) {
+            return plan_lds_bytes(cf, (size_t)n * rows_in * (cols_in + 4), x3, n) <= cf.lds_cap &&
+                   (long long)n * std::min(rows_in, s->H) * s->W * (CKB / 4) <= item_cap;
+        };
+        ds_plan_segmentations(s->B, Ho, Wo, cf.MT(), IS, s->KS, s->KS, fits, [&](int rt, int ni, long long n_mt) {
+            const long long blocks = n_mt * (s->Cout / cf.NTILE());
+            double eff = ds_plan_fill_occupancy(s->B, Ho, Wo, n_mt, cf.MT(), blocks, cf.wg_per_cu);
             // a launch with fewer waves than the chip has SIMDs leaves matrix cores idle: 256 two-wave workgroups (the
             // 10x4 layers of one 256-utterance member) ran 156 us where 256 four-wave ones ran 128 (tools/conv_bf16_ab.py)
-            const long long waves = blocks * (cf.NTHR / 64);
-            if (waves < 1024) eff *= (double)waves / 1024.0;
+            const long long waves = blocks * (cf.NTHR() / 64);
+            if (waves < kPlanSIMDs) eff *= (double)waves / (double)kPlanSIMDs;
             // ties: 160x64 register tiles first; for 64 output channels the four-wave 256x64 tile beats the two-wave
             // 320x64 one (same tool: 484 against 525 us at 768 utterances, 173 against 185 at 256)
             int pref[kNumCfgB] = {0, 2, 7, 8, 5, 6, 1, 4, 3};
@@ -185,7 +151,7 @@ static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride 
 #endif
             eff += 1e-9 * rt + 1e-6 * pref[c];
             if (eff > best) { best = eff; bc = c; brt = rt; bni = ni; }
-        }
+        });
     }
     if (bc < 0) return DS_ERR_UNSUPPORTED;
     const TileCfgB &cf = kCfgB[bc];
@@ -194,30 +160,33 @@ static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride 
     k.Hr = Ho; k.Wc = Wo; k.Ho = yH; k.Wo = yW; k.Cout = s->Cout;
     k.OS = out_stride; k.OH0 = out_h0; k.OW0 = out_w0;
     k.IS = IS; k.dh_min = -pad; k.dw_min = -pad;
-    k.RT = brt; k.NI = bni;
-    k.segs_per_img = ds_ceil_div(Ho, brt);
-    k.n_segs = s->B * k.segs_per_img;
-    k.rows_in = IS * (brt - 1) + s->KS;
-    k.cols_in = IS * (Wo - 1) + s->KS;
+    pl.cfg = bc;
+    ds_plan_fill_geometry(pl, s->B, Ho, Wo, IS, s->KS, s->KS, s->Cout, cf.NTILE(), brt, bni);
     k.half = (k.cols_in + 1) / 2;
     // row pitch: the cheapest fragment read among cols_in .. cols_in+4 records per row
     int best_pitch = k.cols_in;
     double best_cost = 1e30;
     for (int pt = k.cols_in; pt <= k.cols_in + 4; ++pt) {
-        const double c = frag_read_cost(cf.MT, bni, brt, Wo, IS, k.rows_in, pt);
+        const double c = frag_read_cost(cf.MT(), bni, brt, Wo, IS, k.rows_in, pt);
         if (c < best_cost - 1e-9) { best_cost = c; best_pitch = pt; }
     }
     k.pitch = best_pitch;
     k.seg_pix = k.rows_in * k.pitch;
-    k.n_ntiles = s->Cout / cf.NTILE;
     k.y_bytes = (unsigned)((long long)s->B * yH * yW * s->Cout * 4);
-    pl.cfg = bc;
-    pl.n_mtiles = ds_ceil_div(k.n_segs, bni);
-    pl.grid = pl.n_mtiles * k.n_ntiles;
-    const size_t tp = (size_t)k.NI * k.seg_pix;
-    pl.lds_bytes = std::max(tp * PSB * (x3 ? 2 : 1), epi_bytes(cf)) + (size_t)cf.MT * 4 + (size_t)k.NI * 8 + (size_t)cf.WM * cf.NTILE * 8 + 16;
-    pl.nit = ds_ceil_div(k.NI * std::min(k.rows_in, s->H) * s->W * (CKB / 4), cf.NTHR);
+    pl.lds_bytes = plan_lds_bytes(cf, (size_t)k.NI * k.seg_pix, x3, k.NI) + kLdsSlackB;
+    pl.nit = ds_ceil_div(k.NI * std::min(k.rows_in, s->H) * s->W * (CKB / 4), cf.NTHR());
+    // a plain launch until a fused entry point says otherwise: no BatchNorm-backward epilogue
+    k.bn_z = k.bn_mean = k.bn_invstd = k.bn_msc = k.bn_msh = nullptr;
+    k.bn_mtiles = 1; k.bn_rows_member = 0; k.bn_row0 = 0;
     return DS_OK;
+}
+
+// the operands of a launch (every entry point; the fused ones then add the bn_* fields)
+static void set_operands(ConvKB &k, const float *x, const void *w_hi, const void *w_lo, float *y, const float *scale,
+                         const float *shift, const float *res, float *stats, int flags) {
+    k.x = x; k.w_hi = (const __bf16 *)w_hi; k.w_lo = (const __bf16 *)w_lo; k.y = y;
+    k.scale = scale; k.shift = shift; k.res = res; k.stats = stats;
+    k.flags = flags;
 }
 
 // kernel size x arithmetic -> the translation unit that holds those instantiations
@@ -229,10 +198,22 @@ static void launch_b(const PlanB &pl, void *stream) {
 
 }  // namespace
 
-static int pack_bf16(const float *w_oihw, void *w_hi, void *w_lo, int Cout, int Cin, int KS, int dgrad, void *stream) {
+// One filter of a pack call, single or batched; *n = its elements.  The two callers report an unsupported KS with
+// different codes (DS_ERR_BAD_SHAPE from the single-filter entry points, DS_ERR_UNSUPPORTED from the batch): each keeps
+// its code, `bad_ks`.
+static int pack_job_check(const void *w_oihw, const void *w_hi, int Cout, int Cin, int KS, int dgrad, int bad_ks, long long *n) {
     DS_REQUIRE(w_oihw && w_hi, DS_ERR_NULL);
-    DS_REQUIRE(Cout > 0 && Cin > 0 && (KS == 3 || KS == 5) && ((dgrad ? Cout : Cin) % CKB) == 0, DS_ERR_BAD_SHAPE);
-    const long long n = (long long)Cout * Cin * KS * KS;
+    DS_REQUIRE((dgrad == 0 || dgrad == 1) && Cout > 0 && Cin > 0, DS_ERR_BAD_SHAPE);
+    DS_REQUIRE(KS == 3 || KS == 5, bad_ks);
+    DS_REQUIRE((dgrad ? Cout : Cin) % CKB == 0, DS_ERR_BAD_SHAPE);
+    *n = (long long)Cout * Cin * KS * KS;
+    return DS_OK;
+}
+
+static int pack_bf16(const float *w_oihw, void *w_hi, void *w_lo, int Cout, int Cin, int KS, int dgrad, void *stream) {
+    long long n;
+    const int rc = pack_job_check(w_oihw, w_hi, Cout, Cin, KS, dgrad, DS_ERR_BAD_SHAPE, &n);
+    if (rc != DS_OK) return rc;
     long long g = (n + 255) / 256;
     DS_LAUNCH(pack_conv_weight_bf16_kernel, (int)(g > 4096 ? 4096 : g), 256, 0, stream, w_oihw, (__bf16 *)w_hi,
               (__bf16 *)w_lo, Cout, Cin, KS, dgrad);
@@ -247,13 +228,11 @@ extern "C" int ds_pack_conv_weights_bf16_batch(const ds_pack_job *jobs, int n_jo
     int blocks = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const ds_pack_job &b = jobs[j];
-        DS_REQUIRE(b.w_oihw && b.out, DS_ERR_NULL);
-        DS_REQUIRE((b.mode == 0 || b.mode == 1) && b.Cout > 0 && b.Cin > 0, DS_ERR_BAD_SHAPE);
-        DS_REQUIRE(b.KS == 3 || b.KS == 5, DS_ERR_UNSUPPORTED);
-        DS_REQUIRE((b.mode ? b.Cout : b.Cin) % 16 == 0, DS_ERR_BAD_SHAPE);
+        long long n;
+        const int rc = pack_job_check(b.w_oihw, b.out, b.Cout, b.Cin, b.KS, b.mode, DS_ERR_UNSUPPORTED, &n);
+        if (rc != DS_OK) return rc;
         J.w[j] = b.w_oihw; J.hi[j] = (__bf16 *)b.out; J.lo[j] = (__bf16 *)b.out2;
         J.Cout[j] = b.Cout; J.Cin[j] = b.Cin; J.KS[j] = b.KS; J.dgrad[j] = b.mode;
-        const long long n = (long long)b.Cout * b.Cin * b.KS * b.KS;
         const long long g = (n + 255) / 256;
         J.first[j] = blocks;
         blocks += (int)(g > 512 ? 512 : g);
@@ -288,8 +267,8 @@ extern "C" int ds_conv_bf16_plan_describe(const ds_conv_shape *s, int x3, int *o
     int rc = plan_bf16(pl, s, x3 != 0);
     if (rc != DS_OK) return rc;
     const TileCfgB &cf = kCfgB[pl.cfg];
-    out8[0] = cf.MT; out8[1] = cf.NTILE; out8[2] = pl.k.RT; out8[3] = pl.k.NI;
-    out8[4] = pl.grid; out8[5] = (int)pl.lds_bytes; out8[6] = cf.NTHR; out8[7] = pl.k.pitch;
+    out8[0] = cf.MT(); out8[1] = cf.NTILE(); out8[2] = pl.k.RT; out8[3] = pl.k.NI;
+    out8[4] = pl.grid; out8[5] = (int)pl.lds_bytes; out8[6] = cf.NTHR(); out8[7] = pl.k.pitch;
     return DS_OK;
 }
 
@@ -305,11 +284,7 @@ extern "C" int ds_conv_fwd_bf16(const ds_conv_shape *s, const float *x, const vo
     PlanB pl;
     int rc = plan_bf16(pl, s, x3);
     if (rc != DS_OK) return rc;
-    pl.k.x = x; pl.k.w_hi = (const __bf16 *)w_hi; pl.k.w_lo = (const __bf16 *)w_lo; pl.k.y = y;
-    pl.k.scale = scale; pl.k.shift = shift; pl.k.res = residual; pl.k.stats = stats_partial;
-    pl.k.flags = flags;
-    pl.k.bn_z = pl.k.bn_mean = pl.k.bn_invstd = pl.k.bn_msc = pl.k.bn_msh = nullptr;
-    pl.k.bn_mtiles = 1; pl.k.bn_rows_member = 0; pl.k.bn_row0 = 0;
+    set_operands(pl.k, x, w_hi, w_lo, y, scale, shift, residual, stats_partial, flags);
     if (s->KS == 3) { if (x3) launch_b<3, true>(pl, stream); else launch_b<3, false>(pl, stream); }
     else            { if (x3) launch_b<5, true>(pl, stream); else launch_b<5, false>(pl, stream); }
     return ds_last_launch_error();
@@ -355,6 +330,17 @@ extern "C" int ds_pack_conv_weight_dgrad_s2_bf16(const float *w_oihw, void *w_hi
     return ds_last_launch_error();
 }
 
+// One parity class (conv_plan.h) of the 5x5 stride-2 data gradient of forward shape `s`: a 3x3 stride-1 bf16x3
+// convolution over the dY grid whose Hr x Wc outputs land on every other pixel of dX.  The class must not be empty.
+static int plan_s2_class(PlanB &pl, const ds_conv_shape *s, const ds_s2_class &c) {
+    ds_conv_shape t = {s->B, ds_s2_dy_rows(s->H), ds_s2_dy_cols(s->W), s->Cout, s->Cin, 3, 1};
+    return plan_bf16(pl, &t, true, 2, c.ph, c.pw, s->H, s->W, c.Hr, c.Wc);
+}
+// the filter bank of class cls (layout: pack_conv_dgrad_s2_bf16_kernel)
+static const __bf16 *s2_bank(const void *w, const ds_conv_shape *s, int cls) {
+    return (const __bf16 *)w + cls * ((size_t)9 * s->Cout * s->Cin);
+}
+
 // data gradient on the bf16 matrix cores.  3x3 stride 1: the forward kernel on dY with the flipped /
 // transposed bank (ds_pack_conv_weight_dgrad_bf16).  5x5 stride 2: four parity-class launches over the dY
 // grid with the banks of ds_pack_conv_weight_dgrad_s2_bf16, outputs interleaved in dX.
@@ -370,25 +356,13 @@ extern "C" int ds_conv_dgrad_bf16(const ds_conv_shape *s, const float *gy, const
     }
     DS_REQUIRE(s->KS == 5 && s->stride == 2 && gy && w_hi && w_lo && gx, DS_ERR_UNSUPPORTED);
     DS_REQUIRE(DS_ALIGNED16(gy) && DS_ALIGNED16(w_hi) && DS_ALIGNED16(w_lo) && DS_ALIGNED16(gx), DS_ERR_ALIGNMENT);
-    const int Ho = (s->H - 1) / 2 + 1, Wo = (s->W - 1) / 2 + 1;          // dY grid
-    const size_t bank = (size_t)9 * s->Cout * s->Cin;
     for (int cls = 0; cls < 4; ++cls) {
-        const int ph = cls >> 1, pw = cls & 1;
-        const int Hr = (s->H - ph + 1) / 2, Wc = (s->W - pw + 1) / 2;    // dX rows / columns of this parity
-        if (Hr <= 0 || Wc <= 0) continue;
-        ds_conv_shape t = {s->B, Ho, Wo, s->Cout, s->Cin, 3, 1};
+        const ds_s2_class c = ds_s2_class_of(s->H, s->W, cls);
+        if (c.empty()) continue;
         PlanB pl;
-        int rc = plan_bf16(pl, &t, true, 2, ph, pw, s->H, s->W, Hr, Wc);
+        int rc = plan_s2_class(pl, s, c);
         if (rc != DS_OK) return rc;
-        pl.k.x = gy;
-        pl.k.w_hi = (const __bf16 *)w_hi + cls * bank;
-        pl.k.w_lo = (const __bf16 *)w_lo + cls * bank;
-        pl.k.y = gx;
-        pl.k.scale = pl.k.shift = pl.k.res = nullptr;
-        pl.k.stats = nullptr;
-        pl.k.flags = 0;
-        pl.k.bn_z = pl.k.bn_mean = pl.k.bn_invstd = pl.k.bn_msc = pl.k.bn_msh = nullptr;
-        pl.k.bn_mtiles = 1; pl.k.bn_rows_member = 0; pl.k.bn_row0 = 0;
+        set_operands(pl.k, gy, s2_bank(w_hi, s, cls), s2_bank(w_lo, s, cls), gx, nullptr, nullptr, nullptr, nullptr, 0);
         launch_b<3, true>(pl, stream);
         rc = ds_last_launch_error();
         if (rc) return rc;
@@ -396,6 +370,13 @@ extern "C" int ds_conv_dgrad_bf16(const ds_conv_shape *s, const float *gy, const
     return DS_OK;
 }
 
+
+// M tiles per member of a plan whose batch is G members, or DS_ERR_UNSUPPORTED where a tile would straddle two
+static int member_mtiles(const PlanB &pl, int B, int G) {
+    const long long segs_per_member = (long long)(B / G) * pl.k.segs_per_img;
+    DS_REQUIRE(segs_per_member % pl.k.NI == 0, DS_ERR_UNSUPPORTED);
+    return (int)(segs_per_member / pl.k.NI);
+}
 
 // The 3x3 stride-1 data gradient FUSED with the first half of the BatchNorm backward of the layer it feeds
 // (autograd of clip(bn(conv(.))) under loss.backward(), reference train_triplet.py:223 over model.py:69-75,188-203):
@@ -411,10 +392,10 @@ static int plan_bnbwd(PlanB &pl, const ds_conv_shape *s, int G) {
     t.Cout = s->Cin;
     int rc = plan_bf16(pl, &t, true);
     if (rc != DS_OK) return rc;
-    const long long segs_per_member = (long long)(s->B / G) * pl.k.segs_per_img;
-    DS_REQUIRE(segs_per_member % pl.k.NI == 0, DS_ERR_UNSUPPORTED);
-    pl.k.bn_mtiles = (int)(segs_per_member / pl.k.NI);
-    pl.k.bn_rows_member = pl.k.bn_mtiles;
+    const int rows = member_mtiles(pl, s->B, G);
+    if (rows < 0) return rows;
+    pl.k.bn_mtiles = rows;
+    pl.k.bn_rows_member = rows;
     pl.k.bn_row0 = 0;
     return DS_OK;
 }
@@ -436,11 +417,7 @@ extern "C" int ds_conv_dgrad_bnbwd_bf16(const ds_conv_shape *s, const float *gz_
     PlanB pl;
     int rc = plan_bnbwd(pl, s, G);
     if (rc != DS_OK) return rc;
-    pl.k.x = gz_up; pl.k.w_hi = (const __bf16 *)w_hi; pl.k.w_lo = (const __bf16 *)w_lo; pl.k.y = gy;
-    pl.k.scale = pl.k.shift = nullptr;
-    pl.k.res = g2;
-    pl.k.stats = partial;
-    pl.k.flags = DS_EPI_STATS | (g2 ? DS_EPI_RESIDUAL : 0);
+    set_operands(pl.k, gz_up, w_hi, w_lo, gy, nullptr, nullptr, g2, partial, DS_EPI_STATS | (g2 ? DS_EPI_RESIDUAL : 0));
     pl.k.bn_z = z; pl.k.bn_mean = mean; pl.k.bn_invstd = invstd; pl.k.bn_msc = mask_scale; pl.k.bn_msh = mask_shift;
     ds_bf16_launch_k3x3g(pl, stream);
     return ds_last_launch_error();
@@ -449,35 +426,35 @@ extern "C" int ds_conv_dgrad_bnbwd_bf16(const ds_conv_shape *s, const float *gz_
 // The same fusion for the 5x5 stride-2 data gradient, which feeds the activation of a BasicBlock's OUTPUT,
 // out = clip(bn2(conv2(y)) + r) (model.py:76-80): that clip's mask cannot be re-derived from z alone, so it is read from
 // the stored activation `act` ([B,H,W,Cin], the 5x5 layer's input); no second gradient is added.  Four parity-class
-// launches (ds_conv_dgrad_bf16) write interleaved pixels of gy and consecutive blocks of partial rows.
-static int plan_s2_class(PlanB &pl, const ds_conv_shape *s, int cls, int G, int &rows_member) {
-    const int ph = cls >> 1, pw = cls & 1;
-    const int Ho = (s->H - 1) / 2 + 1, Wo = (s->W - 1) / 2 + 1;          // dY grid
-    const int Hr = (s->H - ph + 1) / 2, Wc = (s->W - pw + 1) / 2;        // dX rows / columns of this parity
-    rows_member = 0;
-    if (Hr <= 0 || Wc <= 0) return DS_OK;
-    ds_conv_shape t = {s->B, Ho, Wo, s->Cout, s->Cin, 3, 1};
-    int rc = plan_bf16(pl, &t, true, 2, ph, pw, s->H, s->W, Hr, Wc);
-    if (rc != DS_OK) return rc;
-    const long long segs_per_member = (long long)(s->B / G) * pl.k.segs_per_img;
-    DS_REQUIRE(segs_per_member % pl.k.NI == 0, DS_ERR_UNSUPPORTED);
-    rows_member = (int)(segs_per_member / pl.k.NI);
-    pl.k.bn_mtiles = rows_member;
+// launches (ds_conv_dgrad_bf16) write interleaved pixels of gy and consecutive blocks of partial rows: class cls owns
+// rows[cls] partial rows per member (0: an empty class, not launched), `total` of them together.
+struct S2BnbwdPlans {
+    PlanB pl[4];
+    int rows[4], total;
+};
+
+static int plan_s2_bnbwd(S2BnbwdPlans &P, const ds_conv_shape *s, int G) {
+    DS_REQUIRE(s, DS_ERR_NULL);
+    DS_REQUIRE(s->KS == 5 && s->stride == 2 && G > 0 && s->B % G == 0, DS_ERR_UNSUPPORTED);
+    P.total = 0;
+    for (int cls = 0; cls < 4; ++cls) {
+        const ds_s2_class c = ds_s2_class_of(s->H, s->W, cls);
+        P.rows[cls] = 0;
+        if (c.empty()) continue;
+        int rc = plan_s2_class(P.pl[cls], s, c);
+        if (rc != DS_OK) return rc;
+        const int rows = member_mtiles(P.pl[cls], s->B, G);
+        if (rows < 0) return rows;
+        P.rows[cls] = rows;
+        P.total += rows;
+    }
     return DS_OK;
 }
 
 extern "C" int ds_conv_dgrad_s2_bnbwd_bf16_rows(const ds_conv_shape *s, int G) {
-    DS_REQUIRE(s, DS_ERR_NULL);
-    DS_REQUIRE(s->KS == 5 && s->stride == 2 && G > 0 && s->B % G == 0, DS_ERR_UNSUPPORTED);
-    int total = 0;
-    for (int cls = 0; cls < 4; ++cls) {
-        PlanB pl;
-        int rows = 0;
-        int rc = plan_s2_class(pl, s, cls, G, rows);
-        if (rc != DS_OK) return rc;
-        total += rows;
-    }
-    return total;
+    S2BnbwdPlans P;
+    int rc = plan_s2_bnbwd(P, s, G);
+    return rc == DS_OK ? P.total : rc;
 }
 
 extern "C" int ds_conv_dgrad_s2_bnbwd_bf16(const ds_conv_shape *s, const float *gz_up, const void *w_hi, const void *w_lo,
@@ -487,31 +464,25 @@ extern "C" int ds_conv_dgrad_s2_bnbwd_bf16(const ds_conv_shape *s, const float *
     DS_REQUIRE(s->KS == 5 && s->stride == 2 && G > 0 && s->B % G == 0, DS_ERR_UNSUPPORTED);
     DS_REQUIRE(DS_ALIGNED16(gz_up) && DS_ALIGNED16(w_hi) && DS_ALIGNED16(w_lo) && DS_ALIGNED16(act) && DS_ALIGNED16(z) &&
                    DS_ALIGNED16(gy) && DS_ALIGNED16(mean) && DS_ALIGNED16(invstd), DS_ERR_ALIGNMENT);
-    const int total = ds_conv_dgrad_s2_bnbwd_bf16_rows(s, G);
-    if (total <= 0) return total < 0 ? total : DS_ERR_UNSUPPORTED;
-    const size_t bank = (size_t)9 * s->Cout * s->Cin;
+    S2BnbwdPlans P;
+    int rc = plan_s2_bnbwd(P, s, G);
+    if (rc != DS_OK) return rc;
+    if (P.total <= 0) return DS_ERR_UNSUPPORTED;
     int row0 = 0;
     for (int cls = 0; cls < 4; ++cls) {
-        PlanB pl;
-        int rows = 0;
-        int rc = plan_s2_class(pl, s, cls, G, rows);
-        if (rc != DS_OK) return rc;
-        if (rows == 0) continue;
-        pl.k.x = gz_up;
-        pl.k.w_hi = (const __bf16 *)w_hi + cls * bank;
-        pl.k.w_lo = (const __bf16 *)w_lo + cls * bank;
-        pl.k.y = gy;
-        pl.k.scale = pl.k.shift = nullptr;
-        pl.k.res = act;                                  // the mask's source (not added: bn_msc == nullptr)
-        pl.k.stats = partial;
-        pl.k.flags = DS_EPI_STATS | DS_EPI_RESIDUAL;
-        pl.k.bn_z = z; pl.k.bn_mean = mean; pl.k.bn_invstd = invstd; pl.k.bn_msc = pl.k.bn_msh = nullptr;
-        pl.k.bn_rows_member = total;
+        if (P.rows[cls] == 0) continue;
+        PlanB &pl = P.pl[cls];
+        // res = the mask's source (not added: bn_msc == nullptr)
+        set_operands(pl.k, gz_up, s2_bank(w_hi, s, cls), s2_bank(w_lo, s, cls), gy, nullptr, nullptr, act, partial,
+                     DS_EPI_STATS | DS_EPI_RESIDUAL);
+        pl.k.bn_z = z; pl.k.bn_mean = mean; pl.k.bn_invstd = invstd;
+        pl.k.bn_mtiles = P.rows[cls];
+        pl.k.bn_rows_member = P.total;
         pl.k.bn_row0 = row0;
         ds_bf16_launch_k3x3g(pl, stream);
         rc = ds_last_launch_error();
         if (rc) return rc;
-        row0 += rows;
+        row0 += P.rows[cls];
     }
     return DS_OK;
 }

@@ -4,6 +4,7 @@
 // conv_mfma_bf16.hip.  Design notes: DESIGN_LOG.md section 3.3.
 #pragma once
 #include <ds_device.h>
+#include <type_traits>
 #include "ds_common.h"
 #include "conv_mfma_f16_parts.h"      // ds_mfma_lpix
 
@@ -44,6 +45,37 @@ struct PlanB {
     int cfg, grid, n_mtiles, nit;
     size_t lds_bytes;
     ConvKB k;
+};
+
+// THE tile configurations: a workgroup of WM x WN waves, each wave a register tile of MSUB x NSUB sub-tiles of 32 pixels
+// x 32 output channels.  The planner (conv_mfma_bf16.hip) sizes its plans from the rows, launch_b instantiates the
+// kernels from them; `cfg` everywhere is an index into this table.
+struct TileCfgB {
+    int MSUB, NSUB, WM, WN;
+    int wg_per_cu;                  // resident workgroups per CU
+    size_t lds_cap;                 // bytes of LDS a workgroup may plan with
+    int items_per_thread;           // float4 staging slots a thread has at most (NIT of the kernel)
+    bool x3_only;                   // 160x64 / 128x64 register tiles: tuned for, and only built for, bf16x3; LDS above
+                                    // the default 64 KiB is opted into at launch
+    constexpr int MT() const { return MSUB * WM * 32; }             // pixels per tile
+    constexpr int NTILE() const { return NSUB * WN * 32; }          // output channels per tile
+    constexpr int NTHR() const { return WM * WN * 64; }
+    // the epilogue's per-wave transposition buffers (they alias the pixel tile): EPI_BYTES of the kernel
+    constexpr size_t epi_bytes() const { return (size_t)WM * WN * 32 * (NSUB * 32 + 4) * 4; }
+};
+constexpr int kNumCfgB = 9;
+constexpr TileCfgB kCfgB[kNumCfgB] = {
+    {2, 1, 2, 2, 3, 64 * 1024, 16, false},          // 128 x 64
+    {5, 1, 1, 4, 2, 64 * 1024, 16, false},          // 160 x 128
+    {4, 1, 2, 2, 2, 64 * 1024, 16, false},          // 256 x 64
+    {5, 2, 1, 2, 2, 80 * 1024, 32, true},           // 160 x 128: two waves, 160x64 register tile each, one wave per SIMD
+    // one workgroup per CU, four waves with a 160x64 register tile each and the whole 160 KiB of LDS: the
+    // stride-2 layers, whose input tile is 4x the output tile, keep full M tiles this way
+    {5, 2, 1, 4, 1, 160 * 1024 - 64, 32, true},     // 160 x 256
+    {5, 2, 2, 2, 1, 160 * 1024 - 64, 32, true},     // 320 x 128
+    {5, 2, 2, 1, 2, 80 * 1024, 32, true},           // 320 x 64: the 2-wave shape for 64-channel layers
+    {4, 2, 1, 2, 2, 80 * 1024, 32, true},           // 128 x 128: 128x64 register tiles where 160-row tiles quantise badly
+    {4, 2, 1, 4, 1, 160 * 1024 - 64, 32, true},     // 128 x 256: the same with the whole LDS (three 10x4 maps of the last 5x5 layer)
 };
 
 // one entry point per translation unit (kernel size x arithmetic)
@@ -554,30 +586,33 @@ static void launch_nit_b(const PlanB &pl, void *stream) {
         DS_LAUNCH((conv_mfma_bf16_kernel<KS, MSUB, NSUB, WM, WN, X3, 16, false, BNB>), pl.grid, 256, pl.lds_bytes, stream, pl.k);
 }
 
-template <int KS, int MSUB, int WM, int WN, bool BNB = false>
+template <int KS, int MSUB, int NSUB, int WM, int WN, bool BNB = false>
 static void launch_big_b(const PlanB &pl, void *stream) {
     constexpr int NTHR = WM * WN * 64;
     if (pl.nit <= 8)
-        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, 2, WM, WN, true, 8, true, BNB>), pl.grid, NTHR, pl.lds_bytes, stream, pl.k);
+        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, NSUB, WM, WN, true, 8, true, BNB>), pl.grid, NTHR, pl.lds_bytes, stream, pl.k);
     else if (pl.nit <= 16)
-        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, 2, WM, WN, true, 16, true, BNB>), pl.grid, NTHR, pl.lds_bytes, stream, pl.k);
+        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, NSUB, WM, WN, true, 16, true, BNB>), pl.grid, NTHR, pl.lds_bytes, stream, pl.k);
     else
-        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, 2, WM, WN, true, 32, false, BNB>), pl.grid, NTHR, pl.lds_bytes, stream, pl.k);
+        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, NSUB, WM, WN, true, 32, false, BNB>), pl.grid, NTHR, pl.lds_bytes, stream, pl.k);
+}
+
+// run-time cfg -> compile-time row: f(std::integral_constant<int, cfg>)
+template <int N = 0, class F>
+static void ds_bf16_with_cfg(int cfg, F &&f) {
+    if constexpr (N < kNumCfgB) {
+        if (cfg == N) f(std::integral_constant<int, N>{});
+        else ds_bf16_with_cfg<N + 1>(cfg, f);
+    }
 }
 
 template <int KS, bool X3, bool BNB = false>
 static void launch_b(const PlanB &pl, void *stream) {
-    if (pl.cfg == 0) launch_nit_b<KS, 2, 1, 2, 2, X3, BNB>(pl, stream);
-    else if (pl.cfg == 1) launch_nit_b<KS, 5, 1, 1, 4, X3, BNB>(pl, stream);
-    else if (pl.cfg == 2) launch_nit_b<KS, 4, 1, 2, 2, X3, BNB>(pl, stream);
-    else if constexpr (X3) {                    // 160x64 register tiles, opt-in LDS sizes
-        if (pl.cfg == 3) launch_big_b<KS, 5, 1, 2, BNB>(pl, stream);
-        else if (pl.cfg == 4) launch_big_b<KS, 5, 1, 4, BNB>(pl, stream);
-        else if (pl.cfg == 5) launch_big_b<KS, 5, 2, 2, BNB>(pl, stream);
-        else if (pl.cfg == 6) launch_big_b<KS, 5, 2, 1, BNB>(pl, stream);
-        else if (pl.cfg == 7) launch_big_b<KS, 4, 1, 2, BNB>(pl, stream);
-        else launch_big_b<KS, 4, 1, 4, BNB>(pl, stream);
-    }
+    ds_bf16_with_cfg(pl.cfg, [&](auto c) {
+        constexpr TileCfgB cf = kCfgB[decltype(c)::value];
+        if constexpr (!cf.x3_only) launch_nit_b<KS, cf.MSUB, cf.NSUB, cf.WM, cf.WN, X3, BNB>(pl, stream);
+        else if constexpr (X3) launch_big_b<KS, cf.MSUB, cf.NSUB, cf.WM, cf.WN, BNB>(pl, stream);
+    });
 }
 
 }  // namespace

@@ -7,6 +7,7 @@
 #include "ds_common.h"
 
 #include "conv_mfma_f16_pkernel.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -119,6 +120,8 @@ __global__ void __launch_bounds__(256) conv_f16_splitk_reduce_kernel(const float
 // LDS cycles (1 = conflict-free) of one ds_read_b128 fragment read for candidate row / segment strides: the two
 // 16-lane service groups of lanes 0..31 each hold 16 consecutive pixels of the M tile (`lpix` in the kernel).
 // Bank slot of a record = (byte offset / 16) mod 16; lanes reading the same record do not conflict.
+// NOT the bf16 planner's function of the same name (conv_mfma_bf16.hip): that kernel neither serves equal addresses
+// together nor maps the pixels past the last segment with ds_f16_frag_pixel.
 static double frag_read_cost(int MT, int NI, int RT, int Wc, int IS, int row_bytes, int seg_bytes, int PSH) {
     const int pix_per_seg = RT * Wc;
     double total = 0.0;
@@ -187,18 +190,12 @@ static size_t plan_lds_bytes(const TileCfgH &cf, size_t tile_bytes, int db, int 
     return std::max(tile_bytes * (db ? 2 : 1), cf.epi_bytes()) + (size_t)cf.MT() * 4 + (size_t)NI * 8 + 16;
 }
 
-// The tile search: every launch runs it (resolve_f16), at most twice.
+// The tile search (conv_plan.h, shared with the f32 and bf16 planners): every launch runs it (resolve_f16), at most twice.
 static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, bool force_c16 = false) {
-    DS_REQUIRE(s != nullptr, DS_ERR_NULL);
-    DS_REQUIRE(s->B > 0 && s->H > 0 && s->W > 0 && s->Cin > 0 && s->Cout > 0, DS_ERR_BAD_SHAPE);
-    DS_REQUIRE(s->KS == 3 || s->KS == 5, DS_ERR_UNSUPPORTED);
-    DS_REQUIRE(s->stride == 1 || s->stride == 2, DS_ERR_UNSUPPORTED);
-    DS_REQUIRE(s->Cin % 32 == 0 && s->Cout % 64 == 0, DS_ERR_BAD_SHAPE);
+    int Ho, Wo;
+    const int rc = ds_plan_check_shape(s, 32, false, Ho, Wo);
+    if (rc != DS_OK) return rc;
     const int pad = s->KS / 2;
-    const int Ho = (s->H + 2 * pad - s->KS) / s->stride + 1;
-    const int Wo = (s->W + 2 * pad - s->KS) / s->stride + 1;
-    DS_REQUIRE(Ho > 0 && Wo > 0 && Wo <= 128, DS_ERR_BAD_SHAPE);
-    DS_REQUIRE((long long)s->B * s->H * s->W * s->Cin < (1ll << 31), DS_ERR_BAD_SHAPE);
     DS_REQUIRE((long long)s->B * Ho < (1ll << 24), DS_ERR_BAD_SHAPE);                  // reciprocal index arithmetic
     DS_REQUIRE((long long)s->B * Ho * Wo * s->Cout < (1ll << 30), DS_ERR_BAD_SHAPE);   // 32-bit byte offsets
     const int IS = s->stride;
@@ -218,25 +215,14 @@ static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, boo
             if (force_c16 && s->KS == 5 && mode != 1) continue;
             const int PSH = ds_f16_record_bytes(ck);
             const long long item_cap = (db ? 16 : 32) * cf.NTHR();
-            for (int rt = 1; rt <= Ho; ++rt) {
-                if ((long long)rt * Wo > cf.MT()) break;
-                const int segs_per_img = ds_ceil_div(Ho, rt);
-                const long long n_segs = (long long)s->B * segs_per_img;
-                int ni = cf.MT() / (rt * Wo);
-                if (ni > n_segs) ni = (int)n_segs;
-                const int rows_in = IS * (rt - 1) + s->KS, cols_in = IS * (Wo - 1) + s->KS;
-                auto lds_of = [&](int n) {
-                    const size_t tp = (size_t)n * rows_in * (cols_in + 4);
-                    return std::max((tp * PSH + (size_t)n * 256) * (db ? 2 : 1), cf.epi_bytes()) + (size_t)cf.MT() * 4 + (size_t)n * 8;
-                };
-                auto items_of = [&](int n) { return (long long)n * std::min(rows_in, s->H) * s->W * (ck / 8); };
-                while (ni > 1 && (lds_of(ni) > lds_cap || items_of(ni) > item_cap)) --ni;
-                if (lds_of(ni) > lds_cap || items_of(ni) > item_cap) continue;
-                const long long n_mt = ds_ceil_div_ll(n_segs, ni);
-                double eff = (double)s->B * Ho * Wo / ((double)n_mt * cf.MT());
-                const long long blocks = n_mt * (s->Cout / cf.NTILE()), slots = 256ll * wg_per_cu;
-                if (blocks <= slots) eff *= (double)blocks / (double)(ds_ceil_div_ll(blocks, 256) * 256);
-                else eff *= (double)blocks / (double)(ds_ceil_div_ll(blocks, slots) * slots);
+            // the widest row pitch and 256 bytes of slack per segment (choose_strides); 8-channel items of the in-image pixels
+            auto fits = [&](int n, int rows_in, int cols_in) {
+                const size_t tp = (size_t)n * rows_in * (cols_in + 4);
+                const size_t lds = std::max((tp * PSH + (size_t)n * 256) * (db ? 2 : 1), cf.epi_bytes()) + (size_t)cf.MT() * 4 + (size_t)n * 8;
+                return lds <= lds_cap && (long long)n * std::min(rows_in, s->H) * s->W * (ck / 8) <= item_cap;
+            };
+            ds_plan_segmentations(s->B, Ho, Wo, cf.MT(), IS, s->KS, s->KS, fits, [&](int rt, int ni, long long n_mt) {
+                double eff = ds_plan_fill_occupancy(s->B, Ho, Wo, n_mt, cf.MT(), n_mt * (s->Cout / cf.NTILE()), wg_per_cu);
                 if (mode == 1) eff *= 0.97;
                 if (mode == 2) eff *= (s->KS == 3 ? 0.90 : 0.85);
                 // ties: the four-wave 160 x 256 tile ahead of the two-wave 160 x 128 one (round 5, tools/f16_cfg_ab.py, every
@@ -249,7 +235,7 @@ static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, boo
                 static const int pref3[kNumCfgH] = {3, 6, 5, 1, 4, 2, 0, 0}, pref5[kNumCfgH] = {3, 6, 5, 1, 2, 4, 0, 0};
                 eff += 1e-9 * rt + 1e-6 * (s->KS == 3 ? pref3 : pref5)[c];
                 if (eff > best) { best = eff; bc = c; brt = rt; bni = ni; bdb = db; bck = ck; }
-            }
+            });
         }
     }
     if (bc < 0) return DS_ERR_UNSUPPORTED;
@@ -258,19 +244,12 @@ static int plan_f16(PlanH &pl, const ds_conv_shape *s, bool allow_db = true, boo
     k.H = s->H; k.W = s->W; k.Cin = s->Cin;
     k.Ho = Ho; k.Wo = Wo; k.Cout = s->Cout;
     k.IS = IS; k.dh_min = -pad; k.dw_min = -pad;
-    k.RT = brt; k.NI = bni;
-    k.segs_per_img = ds_ceil_div(Ho, brt);
-    k.n_segs = s->B * k.segs_per_img;
-    k.rows_in = IS * (brt - 1) + s->KS;
-    k.cols_in = IS * (Wo - 1) + s->KS;
+    pl.cfg = bc;
+    ds_plan_fill_geometry(pl, s->B, Ho, Wo, IS, s->KS, s->KS, s->Cout, cf.NTILE(), brt, bni);
     k.half = (k.cols_in + 1) / 2;
     choose_strides(k, cf.MT(), ds_f16_record_bytes(bck));
-    k.n_ntiles = s->Cout / cf.NTILE();
-    pl.cfg = bc;
     pl.db = bdb;
     pl.ck = bck;
-    pl.n_mtiles = ds_ceil_div(k.n_segs, bni);
-    pl.grid = pl.n_mtiles * k.n_ntiles;
     const size_t tile_bytes = (size_t)k.NI * k.seg_bytes;
     pl.lds_bytes = plan_lds_bytes(cf, tile_bytes, bdb, k.NI);
     pl.nit = ds_ceil_div(k.NI * std::min(k.rows_in, s->H) * s->W * (bck / 8), cf.NTHR());

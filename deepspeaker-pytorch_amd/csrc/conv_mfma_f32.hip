@@ -18,6 +18,7 @@
 // input/output strides, the data-gradient convolutions).
 #include <ds_device.h>
 #include "ds_common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -336,7 +337,6 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_mfma_f32_kernel(const ConvK
 // ------------------------------------------------------------------------------------------
 struct TileCfg { int MT, NTILE, NTHR, WM, wg_per_cu; };
 constexpr int kNumCfg = 3;
-constexpr int kNumCU = 256;
 constexpr TileCfg kCfg[kNumCfg] = {
     // wg_per_cu: resident workgroups per CU allowed by the register budget (120 / 256 / 208 regs)
     {128, 64, 256, 2, 4},     // conv_mfma_f32_kernel<KS,2,1,2,2,*>
@@ -353,10 +353,9 @@ struct ConvPlan {
     ConvK k;
 };
 
-// Choose (cfg, RT, NI): maximise (fraction of MFMA rows that are real pixels) x (occupancy of the
-// last round of workgroups), then tile size and segment height.  Full-width segments only.
-static int plan_tiles(ConvPlan &pl, int B, int Hr, int Wc, int IS, int ext_h, int ext_w, int Cout,
-                      bool stats) {
+// Choose (cfg, RT, NI): the shared tile search (conv_plan.h) -- maximise (fraction of MFMA rows that are real pixels)
+// x (occupancy of the last round of workgroups), then tile size and segment height.  Full-width segments only.
+static int plan_tiles(ConvPlan &pl, int B, int Hr, int Wc, int IS, int ext_h, int ext_w, int Cout) {
     DS_REQUIRE((long long)B * pl.k.Ho * pl.k.Wo * pl.k.Cout < (1ll << 30), DS_ERR_BAD_SHAPE);   // 32-bit byte offsets
     pl.k.y_bytes = (unsigned)((long long)B * pl.k.Ho * pl.k.Wo * pl.k.Cout * 4);
     double best_eff = -1.0;
@@ -364,71 +363,44 @@ static int plan_tiles(ConvPlan &pl, int B, int Hr, int Wc, int IS, int ext_h, in
     for (int c = 0; c < kNumCfg; ++c) {
         const TileCfg &cf = kCfg[c];
         if (Cout % cf.NTILE) continue;
-        for (int rt = 1; rt <= Hr; ++rt) {
-            if ((long long)rt * Wc > cf.MT) break;
-            const int segs_per_img = ds_ceil_div(Hr, rt);
-            const long long n_segs = (long long)B * segs_per_img;
-            int ni = cf.MT / (rt * Wc);
-            if (ni > n_segs) ni = (int)n_segs;
-            const int rows_in = IS * (rt - 1) + ext_h, cols_in = IS * (Wc - 1) + ext_w;
-            while (ni > 1 && (long long)ni * rows_in * cols_in * (CK / 4) > (long long)MAX_STAGE_IT * cf.NTHR) --ni;
-            if ((long long)ni * rows_in * cols_in * (CK / 4) > (long long)MAX_STAGE_IT * cf.NTHR) continue;
-            const long long n_mt = ds_ceil_div_ll(n_segs, ni);
-            double eff = (double)B * Hr * Wc / ((double)n_mt * cf.MT);
-            // wave quantisation: the grid runs in rounds of (CUs x resident workgroups); a half-empty
-            // last round idles matrix cores just like masked rows do
-            // (measured: 768 workgroups at 2/CU run at 0.84 of the rate of 256 or 512).  A grid that
-            // fits in one round is spread evenly over the CUs by the dispatcher.
-            const long long blocks = n_mt * (Cout / cf.NTILE), slots = (long long)kNumCU * cf.wg_per_cu;
-            if (blocks <= slots) eff *= (double)blocks / (double)(ds_ceil_div_ll(blocks, kNumCU) * kNumCU);
-            else eff *= (double)blocks / (double)(ds_ceil_div_ll(blocks, slots) * slots);
+        // the whole input tile is staged, halo included: MAX_STAGE_IT float4 slots per thread
+        auto fits = [&](int ni, int rows_in, int cols_in) {
+            return (long long)ni * rows_in * cols_in * (CK / 4) <= (long long)MAX_STAGE_IT * cf.NTHR;
+        };
+        ds_plan_segmentations(B, Hr, Wc, cf.MT, IS, ext_h, ext_w, fits, [&](int rt, int ni, long long n_mt) {
+            double eff = ds_plan_fill_occupancy(B, Hr, Wc, n_mt, cf.MT, n_mt * (Cout / cf.NTILE), cf.wg_per_cu);
             // ties: bigger tiles (more MFMAs per staged byte and per barrier), taller segments
             eff += 1e-9 * rt + 1e-6 * (c == 1 ? 2 : (c == 2 ? 1 : 0));
             if (eff > best_eff) { best_eff = eff; best_cfg = c; best_rt = rt; best_ni = ni; }
-        }
+        });
     }
     if (best_cfg < 0) return DS_ERR_UNSUPPORTED;
     const TileCfg &cf = kCfg[best_cfg];
     ConvK &k = pl.k;
-    k.RT = best_rt;
-    k.NI = best_ni;
-    k.segs_per_img = ds_ceil_div(Hr, best_rt);
-    k.n_segs = B * k.segs_per_img;
-    k.rows_in = IS * (best_rt - 1) + ext_h;
-    k.cols_in = IS * (Wc - 1) + ext_w;
-    k.seg_pix = k.rows_in * k.cols_in;
-    k.n_ntiles = Cout / cf.NTILE;
     pl.cfg = best_cfg;
-    pl.n_mtiles = ds_ceil_div(k.n_segs, best_ni);
-    pl.grid = pl.n_mtiles * k.n_ntiles;
+    ds_plan_fill_geometry(pl, B, Hr, Wc, IS, ext_h, ext_w, Cout, cf.NTILE, best_rt, best_ni);
+    k.seg_pix = k.rows_in * k.cols_in;
     const int items = k.NI * k.seg_pix * (CK / 4);
     const int its = ds_ceil_div(items, cf.NTHR);
     pl.nit = its <= 2 ? 2 : (its <= 4 ? 4 : 8);
     // pixel tile + row table + statistics scratch + the 16-byte dump slot
     pl.lds_bytes = (size_t)k.NI * k.seg_pix * LDS_PS * 4 + (size_t)cf.MT * 4 + (size_t)cf.WM * cf.NTILE * 2 * 4 + 16;
-    (void)stats;
     return DS_OK;
 }
 
-static int plan_forward(ConvPlan &pl, const ds_conv_shape *s, bool stats) {
-    DS_REQUIRE(s != nullptr, DS_ERR_NULL);
-    DS_REQUIRE(s->B > 0 && s->H > 0 && s->W > 0 && s->Cin > 0 && s->Cout > 0, DS_ERR_BAD_SHAPE);
-    DS_REQUIRE(s->KS == 1 || s->KS == 3 || s->KS == 5, DS_ERR_UNSUPPORTED);
-    DS_REQUIRE(s->stride == 1 || s->stride == 2, DS_ERR_UNSUPPORTED);
-    DS_REQUIRE(s->Cin % CK == 0 && s->Cout % 64 == 0, DS_ERR_BAD_SHAPE);
-    const int pad = s->KS / 2;
-    const int Ho = (s->H + 2 * pad - s->KS) / s->stride + 1;
-    const int Wo = (s->W + 2 * pad - s->KS) / s->stride + 1;
-    DS_REQUIRE(Ho > 0 && Wo > 0 && Wo <= 128, DS_ERR_BAD_SHAPE);
-    DS_REQUIRE((long long)s->B * s->H * s->W * s->Cin < (1ll << 31), DS_ERR_BAD_SHAPE);
+static int plan_forward(ConvPlan &pl, const ds_conv_shape *s) {
+    int Ho, Wo;
+    int rc = ds_plan_check_shape(s, CK, true, Ho, Wo);
+    if (rc != DS_OK) return rc;
     DS_REQUIRE((long long)s->B * Ho * Wo * s->Cout < (1ll << 31), DS_ERR_BAD_SHAPE);
+    const int pad = s->KS / 2;
     ConvK &k = pl.k;
     k.H = s->H; k.W = s->W; k.Cin = s->Cin;
     k.Hr = Ho; k.Wc = Wo; k.Ho = Ho; k.Wo = Wo; k.Cout = s->Cout;
     k.IS = s->stride; k.OS = 1; k.OH0 = 0; k.OW0 = 0;
     k.NT = s->KS * s->KS;
     k.dh_min = -pad; k.dw_min = -pad;
-    int rc = plan_tiles(pl, s->B, Ho, Wo, s->stride, s->KS, s->KS, s->Cout, stats);
+    rc = plan_tiles(pl, s->B, Ho, Wo, s->stride, s->KS, s->KS, s->Cout);
     if (rc != DS_OK) return rc;
     for (int kh = 0; kh < s->KS; ++kh)
         for (int kw = 0; kw < s->KS; ++kw) k.tap_off[kh * s->KS + kw] = kh * k.cols_in + kw;
@@ -473,7 +445,7 @@ extern "C" int ds_conv_out_dims(const ds_conv_shape *s, int *Ho, int *Wo) {
 
 extern "C" int ds_conv_stats_rows(const ds_conv_shape *s) {
     ConvPlan pl;
-    int rc = plan_forward(pl, s, true);
+    int rc = plan_forward(pl, s);
     return rc == DS_OK ? pl.n_mtiles : rc;
 }
 
@@ -506,7 +478,7 @@ extern "C" int ds_conv_dgrad_f32(const ds_conv_shape *s, const float *gy, const 
         t.Cin = s->Cout;
         t.Cout = s->Cin;
         ConvPlan pl;
-        rc = plan_forward(pl, &t, false);
+        rc = plan_forward(pl, &t);
         if (rc != DS_OK) return rc;
         pl.k.x = gy; pl.k.w = w_dgrad_packed; pl.k.y = gx;
         pl.k.scale = pl.k.shift = pl.k.res = nullptr; pl.k.stats = nullptr;
@@ -517,40 +489,39 @@ extern "C" int ds_conv_dgrad_f32(const ds_conv_shape *s, const float *gy, const 
     DS_REQUIRE(s->Cout % CK == 0 && s->Cin % 64 == 0, DS_ERR_BAD_SHAPE);
     DS_REQUIRE((long long)s->B * s->H * s->W * s->Cin < (1ll << 31), DS_ERR_BAD_SHAPE);
     size_t w_off = 0;
-    for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw) {
-            int kh[3], dh[3], kw[3], dw[3];
-            const int nh = s2_class_taps(ph, kh, dh), nw = s2_class_taps(pw, kw, dw);
-            const int nt = nh * nw;
-            const int Hr = (s->H - ph + 1) / 2, Wc = (s->W - pw + 1) / 2;
-            const size_t w_this = w_off;
-            w_off += (size_t)nt * s->Cout * s->Cin;
-            if (Hr <= 0 || Wc <= 0) continue;
-            ConvPlan pl;
-            ConvK &k = pl.k;
-            k.H = Ho; k.W = Wo; k.Cin = s->Cout;
-            k.Hr = Hr; k.Wc = Wc; k.Ho = s->H; k.Wo = s->W; k.Cout = s->Cin;
-            k.IS = 1; k.OS = 2; k.OH0 = ph; k.OW0 = pw;
-            k.NT = nt;
-            const int dh_min = dh[nh - 1], dw_min = dw[nw - 1];       // offsets descend with the kernel index
-            k.dh_min = dh_min; k.dw_min = dw_min;
-            rc = plan_tiles(pl, s->B, Hr, Wc, 1, nh, nw, s->Cin, false);
-            if (rc != DS_OK) return rc;
-            for (int i = 0; i < nh; ++i)
-                for (int j = 0; j < nw; ++j) k.tap_off[i * nw + j] = (dh[i] - dh_min) * k.cols_in + (dw[j] - dw_min);
-            k.x = gy; k.w = w_dgrad_packed + w_this; k.y = gx;
-            k.scale = k.shift = k.res = nullptr; k.stats = nullptr;
-            k.flags = 0;
-            rc = launch(pl, 0, stream);
-            if (rc != DS_OK) return rc;
-        }
+    for (int cls = 0; cls < 4; ++cls) {
+        const ds_s2_class c = ds_s2_class_of(s->H, s->W, cls);
+        int kh[3], dh[3], kw[3], dw[3];
+        const int nh = s2_class_taps(c.ph, kh, dh), nw = s2_class_taps(c.pw, kw, dw);
+        const int nt = nh * nw;
+        const size_t w_this = w_off;
+        w_off += (size_t)nt * s->Cout * s->Cin;
+        if (c.empty()) continue;
+        ConvPlan pl;
+        ConvK &k = pl.k;
+        k.H = Ho; k.W = Wo; k.Cin = s->Cout;
+        k.Hr = c.Hr; k.Wc = c.Wc; k.Ho = s->H; k.Wo = s->W; k.Cout = s->Cin;
+        k.IS = 1; k.OS = 2; k.OH0 = c.ph; k.OW0 = c.pw;
+        k.NT = nt;
+        const int dh_min = dh[nh - 1], dw_min = dw[nw - 1];       // offsets descend with the kernel index
+        k.dh_min = dh_min; k.dw_min = dw_min;
+        rc = plan_tiles(pl, s->B, c.Hr, c.Wc, 1, nh, nw, s->Cin);
+        if (rc != DS_OK) return rc;
+        for (int i = 0; i < nh; ++i)
+            for (int j = 0; j < nw; ++j) k.tap_off[i * nw + j] = (dh[i] - dh_min) * k.cols_in + (dw[j] - dw_min);
+        k.x = gy; k.w = w_dgrad_packed + w_this; k.y = gx;
+        k.scale = k.shift = k.res = nullptr; k.stats = nullptr;
+        k.flags = 0;
+        rc = launch(pl, 0, stream);
+        if (rc != DS_OK) return rc;
+    }
     return DS_OK;
 }
 
 extern "C" int ds_conv_plan_describe(const ds_conv_shape *s, int *out8) {
     DS_REQUIRE(out8, DS_ERR_NULL);
     ConvPlan pl;
-    int rc = plan_forward(pl, s, false);
+    int rc = plan_forward(pl, s);
     if (rc != DS_OK) return rc;
     out8[0] = kCfg[pl.cfg].MT; out8[1] = kCfg[pl.cfg].NTILE; out8[2] = pl.k.RT; out8[3] = pl.k.NI;
     out8[4] = pl.grid; out8[5] = (int)pl.lds_bytes; out8[6] = pl.nit; out8[7] = pl.n_mtiles;
@@ -566,7 +537,7 @@ extern "C" int ds_conv_fwd_f32(const ds_conv_shape *s, const float *x, const flo
     DS_REQUIRE(!(flags & DS_EPI_STATS) || stats_partial, DS_ERR_NULL);
     DS_REQUIRE(DS_ALIGNED16(x) && DS_ALIGNED16(w_packed) && DS_ALIGNED16(y), DS_ERR_ALIGNMENT);
     ConvPlan pl;
-    int rc = plan_forward(pl, s, (flags & DS_EPI_STATS) != 0);
+    int rc = plan_forward(pl, s);
     if (rc != DS_OK) return rc;
     pl.k.x = x; pl.k.w = w_packed; pl.k.y = y;
     pl.k.scale = scale; pl.k.shift = shift; pl.k.res = residual; pl.k.stats = stats_partial;

@@ -9,6 +9,7 @@ import pytest
 
 import deepspeaker_oracle as O
 from conftest import rel_err
+from conv_cases import BF16_CASES, CASES, DGRAD_BF16_CASES, DGRAD_CASES
 from emul_util import aligned, emul_lib, nchw, nhwc, ptr, to_aligned
 from deepspeaker_pytorch_amd._native import (ConvShape, DS_EPI_AFFINE, DS_EPI_CLIP, DS_EPI_RESIDUAL,
                                              DS_EPI_STATS)
@@ -42,19 +43,6 @@ def run_conv(lib, x_nchw, w, stride, flags=0, scale=None, shift=None, res_nchw=N
     lib.call("ds_conv_fwd_f32", ctypes.byref(shp), ptr(xh), ptr(wp), ptr(sc), ptr(sh), ptr(rh), ptr(y),
              ptr(stats), flags, None)
     return nchw(y), stats
-
-
-CASES = [
-    # (B, Cin, Cout, H, W, KS, stride)       what it exercises
-    (2, 8, 64, 9, 32, 3, 1),                 # stage-1 geometry, partial last row block (9 = 2*4+1)
-    (1, 16, 64, 8, 16, 3, 1),                # two channel chunks, 8-row segments
-    (3, 8, 128, 20, 8, 3, 1),                # stage-3 geometry: whole image = 160 rows, 160x128 tile
-    (5, 8, 128, 10, 4, 3, 1),                # stage-4 geometry: 4 images per tile, ragged last tile
-    (2, 8, 64, 16, 32, 5, 2),                # 5x5 stride 2, even sizes
-    (2, 8, 128, 13, 16, 5, 2),               # 5x5 stride 2, odd height (variable-length utterances)
-    (3, 16, 128, 7, 8, 5, 2),                # 5x5 s2 into a 4x4 map, multi-image tiles
-    (70, 24, 64, 1, 1, 1, 1),                # 1x1 on [B,1,1,C]: the fc GEMM shape class
-]
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -147,12 +135,6 @@ def test_conv1(shape):
 # ------------------------------------------------------------------------------------------------
 # backward kernels
 # ------------------------------------------------------------------------------------------------
-DGRAD_CASES = [
-    (2, 64, 8, 9, 32, 3, 1), (3, 128, 16, 20, 8, 3, 1),
-    (2, 64, 8, 16, 32, 5, 2), (2, 64, 16, 13, 16, 5, 2), (3, 128, 8, 7, 8, 5, 2), (1, 64, 8, 1, 4, 5, 2),
-]
-
-
 @pytest.mark.parametrize("case", DGRAD_CASES)
 def test_conv_dgrad(case):
     """dL/dx of nn.Conv2d: flipped-filter convolution (stride 1) / four parity-class convolutions (stride 2)."""
@@ -174,10 +156,6 @@ def test_conv_dgrad(case):
     shp = ConvShape(b, h, w, ci, co, k, s)
     lib.call("ds_conv_dgrad_f32", ctypes.byref(shp), ptr(gyh), ptr(wp), ptr(gx), None)
     assert rel_err(nchw(gx), gx_ref) < 2e-6
-
-
-DGRAD_BF16_CASES = [(2, 64, 64, 9, 32, 3, 1), (2, 64, 64, 16, 32, 5, 2), (2, 64, 16, 13, 16, 5, 2),
-                    (3, 128, 64, 7, 8, 5, 2), (1, 64, 32, 1, 4, 5, 2)]
 
 
 @pytest.mark.parametrize("case", DGRAD_BF16_CASES)
@@ -469,12 +447,6 @@ def test_pairwise_distance_any_norm(p):
     s = (np.abs(diff) ** p).sum(1) + 1e-4 / D
     want = gd[:, None] * (s ** (1.0 / p - 1.0))[:, None] * np.abs(diff) ** (p - 1.0) * np.sign(diff)
     assert rel_err(g1, want.astype(np.float32)) < 5e-6
-
-
-BF16_CASES = [
-    (2, 16, 64, 9, 32, 3, 1), (3, 32, 128, 20, 8, 3, 1), (5, 16, 128, 10, 4, 3, 1),
-    (2, 16, 64, 16, 32, 5, 2), (2, 32, 128, 13, 16, 5, 2), (3, 16, 128, 7, 8, 5, 2),
-]
 
 
 @pytest.mark.parametrize("x3", [True, False])
