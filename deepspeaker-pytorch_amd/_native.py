@@ -193,6 +193,8 @@ _SIGNATURES = {
                                     _P, _P, _P]),
     "ds_fbank_preemphasis_f32": (c_int, [_P, c_int, c_longlong, _P, _P]),
     "ds_fbank_normalize_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "ds_resample_plan": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "ds_resample_poly_f32": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, _P, _P]),
 }
 
 

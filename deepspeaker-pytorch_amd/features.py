@@ -7,10 +7,15 @@ nfilt=64, winlen=0.025 (pre-emphasis 0.97, rectangular window, 512-point power s
 divide by std + 2e-12).  Here the whole batch is one HIP call chain (csrc/fbank.hip): the DFT runs as an f32 MFMA GEMM
 against a cos/sin basis built once per configuration, and the result is packed [sum T_u, nfilt] f32 on the device,
 ready for `data.FeatureStore.from_waveforms`.  Frame counts follow from the host-side lengths: no read-back.
+
+Audio at another rate, or with several channels, goes through `resample` first (csrc/resample.hip): the resampling and
+mono down-mix of the reference's `librosa.load(filename, sr=16000, mono=True)` (audio_processing.py:10) as one rational
+polyphase filter with SciPy's `resample_poly` design.  Decoding files stays on the host.
 """
 from __future__ import annotations
 
 import decimal
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple, Union
 
@@ -108,25 +113,15 @@ def _device_tables(config: FbankConfig, device: torch.device):
     return hit
 
 
-def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config: FbankConfig = FbankConfig(),
-                  normalize: Optional[str] = "mean", lengths: Optional[Sequence[int]] = None
-                  ) -> Tuple[torch.Tensor, np.ndarray]:
-    """mk_MFB of every waveform in one call chain on the waveforms' device.
-
-    `waveforms`: a sequence of 1-D tensors (float32 samples, or int16 PCM, which is scaled by 1/32768), or ONE packed
-    1-D tensor with the host `lengths` of its utterances.  `normalize`: "mean" (the reference's USE_SCALE=False),
-    "mean_std" (USE_SCALE=True) or None (raw log filterbank; with config.use_logscale=False the raw filterbank).
-    Returns the packed [sum T_u, nfilt] float32 features on the device and the host int64 frame offsets [n_utt + 1]:
-    utterance u is rows offsets[u]:offsets[u+1].  Deltas, resampling and decoding are the caller's."""
-    if normalize not in _NORMALIZE:
-        raise ValueError(f"normalize must be one of {_NORMALIZE}, got {normalize!r}")
-    eng = _eng()
+def _pack(waveforms, lengths, channels: int = 1):
+    """(packed 1-D tensor, host int64 lengths) of either input form; with `channels` > 1 the samples are interleaved
+    and the lengths count frames."""
     if isinstance(waveforms, torch.Tensor):
         if lengths is None or waveforms.dim() != 1:
             raise ValueError("a packed waveform tensor must be 1-D and come with the host `lengths` of its utterances")
         packed = waveforms.contiguous()
         lens = np.asarray(lengths, np.int64)
-        if lens.ndim != 1 or int(lens.sum()) != packed.numel():
+        if lens.ndim != 1 or int(lens.sum()) * channels != packed.numel():
             raise ValueError("lengths must sum to the packed tensor's length")
     else:
         if lengths is not None:
@@ -135,10 +130,127 @@ def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config
             raise ValueError("no waveforms")
         if any(w.dim() != 1 for w in waveforms) or len({w.dtype for w in waveforms}) != 1:
             raise ValueError("waveforms must be 1-D tensors of one dtype")
-        lens = np.array([w.numel() for w in waveforms], np.int64)
+        if any(w.numel() % channels for w in waveforms):
+            raise ValueError(f"every waveform must hold whole frames of {channels} interleaved channels")
+        lens = np.array([w.numel() // channels for w in waveforms], np.int64)
         packed = waveforms[0].contiguous() if len(waveforms) == 1 else torch.cat(list(waveforms))
     if packed.dtype not in (torch.float32, torch.int16):
         raise ValueError(f"waveforms must be float32 or int16, got {packed.dtype}")
+    return packed, lens
+
+
+def _upload(table: np.ndarray, dev: torch.device) -> torch.Tensor:
+    """A host plan table on `dev`: through pinned memory, without blocking the host (a pageable copy waits for the
+    stream's queue)."""
+    table_t = torch.from_numpy(table)
+    return table_t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else table_t
+
+
+MAX_CHANNELS = 8
+
+
+def resample_taps(L: int, M: int, zeros: int = 10, beta: float = 5.0) -> np.ndarray:
+    """The float64 low-pass table h[0 .. 2H] of `scipy.signal.resample_poly(x, L, M, window=("kaiser", beta))`: with
+    q = max(L, M) and H = zeros * q, h = L * w / sum(w), w[i] = sinc((i - H) / q) / q * kaiser(2H + 1, beta)[i].  The
+    sinc's zero crossings (i - H a non-zero multiple of q), where np.sinc leaves a residue of 4e-17, are exact zeros: at
+    L = M = 1 the table is the unit impulse and resampling returns its input's bits."""
+    q = max(int(L), int(M))
+    H = int(zeros) * q
+    i = np.arange(2 * H + 1) - H
+    w = np.sinc(i / q) / q * np.kaiser(2 * H + 1, beta)
+    w[(i % q == 0) & (i != 0)] = 0.0
+    return L * w / w.sum()
+
+
+def polyphase_taps(h: np.ndarray, L: int) -> np.ndarray:
+    """[L, T | 1] float32, T = ceil(len(h) / L): row p holds h[p], h[p + L], ... in REVERSE (the order of ascending input
+    index), zero where the table has no tap and in the padding column (an odd row stride for the LDS banks)."""
+    T = -(-len(h) // L)
+    full = np.zeros(L * T)
+    full[:len(h)] = h
+    out = np.zeros((L, T | 1), np.float32)
+    out[:, :T] = full.reshape(T, L).T[:, ::-1]
+    return out
+
+
+_taps = {}
+
+
+def _device_taps(L: int, M: int, zeros: int, beta: float, device: torch.device) -> torch.Tensor:
+    key = (L, M, zeros, beta, str(device))
+    hit = _taps.get(key)
+    if hit is None:
+        hit = torch.from_numpy(polyphase_taps(resample_taps(L, M, zeros, beta), L)).to(device)
+        _taps[key] = hit
+    return hit
+
+
+def resample(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], orig_rate: int, new_rate: int = 16000,
+             channels: int = 1, zeros: int = 10, beta: float = 5.0, lengths: Optional[Sequence[int]] = None
+             ) -> Tuple[torch.Tensor, np.ndarray]:
+    """Waveforms at `orig_rate` as mono float32 at `new_rate`, in one kernel on the waveforms' device.
+
+    `waveforms`: as for `log_mel_fbank` (a sequence of 1-D float32 / int16 tensors, or one packed 1-D tensor with the
+    host `lengths`).  With `channels` > 1 (up to 8) the samples are interleaved [frames, channels], the lengths count
+    frames, and the channels are averaged first (summed in order and divided in float32: librosa's mono=True).  The
+    filter is `resample_taps(new_rate / g, orig_rate / g, zeros, beta)`, g the rates' gcd: utterance u of n samples
+    becomes ceil(n * new_rate / orig_rate) samples, as scipy.signal.resample_poly makes them.  Returns the packed 1-D
+    float32 result on the device and the host int64 lengths, which feed `log_mel_fbank(packed, lengths=lengths)`."""
+    if int(orig_rate) != orig_rate or int(new_rate) != new_rate or orig_rate < 1 or new_rate < 1:
+        raise ValueError(f"sample rates must be positive integers, got {orig_rate!r} -> {new_rate!r}")
+    if int(channels) != channels or not 1 <= channels <= MAX_CHANNELS:
+        raise ValueError(f"channels must be 1 .. {MAX_CHANNELS}, got {channels!r}")
+    if int(zeros) != zeros or zeros < 1:
+        raise ValueError(f"zeros must be a positive integer, got {zeros!r}")
+    orig_rate, new_rate, channels, zeros, beta = int(orig_rate), int(new_rate), int(channels), int(zeros), float(beta)
+    eng = _eng()
+    packed, lens = _pack(waveforms, lengths, channels)
+    dev = packed.device
+    n_utt = len(lens)
+    g = math.gcd(orig_rate, new_rate)
+    L, M = new_rate // g, orig_rate // g
+    half = zeros * max(L, M)
+
+    # output lengths, offsets and the tile table on the host (the lengths are host data)
+    counts = np.zeros(3, np.int64)
+    lens_c = np.ascontiguousarray(lens)
+    plan = lambda table: eng.lib.call("ds_resample_plan", lens_c.ctypes.data, n_utt, L, M, half,
+                                      None if table is None else table.ctypes.data, counts.ctypes.data)
+    plan(None)
+    n_out, n_tiles = int(counts[0]), int(counts[1])
+    table = np.zeros(3 * (n_utt + 1) + n_tiles, np.int64)
+    plan(table)
+    out_lens = np.diff(table[n_utt + 1:2 * (n_utt + 1)])
+    table_dev = _upload(table, dev)
+
+    taps = _device_taps(L, M, zeros, beta, dev)
+    out = torch.empty(n_out, dtype=torch.float32, device=dev)
+    eng.lib.call("ds_resample_poly_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, channels,
+                 eng._p(table_dev), n_utt, n_tiles, eng._p(taps), L, M, half, eng._p(out), eng._stream(out))
+    return out, out_lens
+
+
+def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config: FbankConfig = FbankConfig(),
+                  normalize: Optional[str] = "mean", lengths: Optional[Sequence[int]] = None, *,
+                  orig_rate: Optional[int] = None, channels: int = 1) -> Tuple[torch.Tensor, np.ndarray]:
+    """mk_MFB of every waveform in one call chain on the waveforms' device.
+
+    `waveforms`: a sequence of 1-D tensors (float32 samples, or int16 PCM, which is scaled by 1/32768), or ONE packed
+    1-D tensor with the host `lengths` of its utterances.  `normalize`: "mean" (the reference's USE_SCALE=False),
+    "mean_std" (USE_SCALE=True) or None (raw log filterbank; with config.use_logscale=False the raw filterbank).
+    `orig_rate` / `channels`: the waveforms' own sample rate and interleaved channel count; given, they are first
+    resampled to config.sample_rate and mixed down to mono on the device (`resample`), which together with this
+    function is the reference's librosa.load(..., sr=16000, mono=True) followed by mk_MFB.
+    Returns the packed [sum T_u, nfilt] float32 features on the device and the host int64 frame offsets [n_utt + 1]:
+    utterance u is rows offsets[u]:offsets[u+1].  Decoding files is the caller's; deltas are not computed (the
+    reference's USE_DELTA is False)."""
+    if normalize not in _NORMALIZE:
+        raise ValueError(f"normalize must be one of {_NORMALIZE}, got {normalize!r}")
+    if orig_rate is not None or channels != 1:
+        waveforms, lengths = resample(waveforms, config.sample_rate if orig_rate is None else orig_rate,
+                                      config.sample_rate, channels, lengths=lengths)
+    eng = _eng()
+    packed, lens = _pack(waveforms, lengths)
     dev = packed.device
     n_utt = len(lens)
     fl, fs, nfft, nfilt = config.frame_len, config.frame_step, config.nfft, config.nfilt
@@ -153,9 +265,7 @@ def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config
     table = np.zeros(3 * (n_utt + 1) + n_tiles, np.int64)
     plan(table)
     offsets = table[n_utt + 1:2 * (n_utt + 1)].copy()
-    table_t = torch.from_numpy(table)
-    # through pinned memory, without blocking the host (a pageable copy waits for the stream's queue)
-    table_dev = table_t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else table_t
+    table_dev = _upload(table, dev)
 
     basis, band, weights, wstride = _device_tables(config, dev)
     out = torch.empty((n_frames, nfilt), dtype=torch.float32, device=dev)

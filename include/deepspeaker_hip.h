@@ -87,7 +87,8 @@ int ds_version(void);            /* 100: round 1; 200: round 2 (fp16 path, group
                                     400: round 4 (fp16 training step: ds_*_f16 train entry points, ds_wgrad_f16, probes of the
                                     near-tie refinement, launch-bound timing); 500: round 5; 600: round 6 (caller-owned
                                     scheduler workspace); 700: log-mel filterbank front end (ds_fbank_*); 800: speaker identification
-                                    (ds_nearest_*, ds_segment_mean_rows_f32, ds_rank_hits_i32) */
+                                    (ds_nearest_*, ds_segment_mean_rows_f32, ds_rank_hits_i32); 900: polyphase resampler
+                                    (ds_resample_plan, ds_resample_poly_f32) */
 /* launch timing without marker packets: the next MFMA convolution / filter-gradient launch of the calling thread
  * records its own execution into the armed pair (hipExtLaunchKernelGGL); ds_launch_timing_end() disarms and returns
  * how many such launches happened since arming (1 = the timed call was a single kernel) */
@@ -700,6 +701,30 @@ int ds_fbank_logmel_f32(const void *samples, int in_int16, const long long *tabl
 int ds_fbank_preemphasis_f32(const void *samples, int in_int16, long long n, float *out, void *stream);
 int ds_fbank_normalize_f32(float *feat, const long long *table, int n_utt, int n_tiles, int nfilt, int tile_rows,
                            int use_scale, double *workspace, void *stream);
+
+/* ---- rational polyphase resampler (resample.hip): packed waveforms at one rate -> packed mono f32 at another, the
+ * resampling and down-mix of the reference's librosa.load(filename, sr=16000, mono=True).  With up = new_rate / g and
+ * down = orig_rate / g (g their gcd) and a windowed-sinc table h of 2 * half_width + 1 taps,
+ *   y[m] = sum_k x[k] * h[half_width + m * down - k * up]   (0 <= k < n, taps outside the table are zero),
+ *   n_out = ceil(n * up / down).
+ * Every output is one fmaf chain over ascending k: deterministic, independent of tile, batch and call.  Every buffer is
+ * the caller's.
+ * ds_resample_plan (HOST): from the host frame counts `lengths[n_utt]`.  With table == NULL only counts[3] = {total
+ *   outputs, tiles, outputs per tile} is written; otherwise also the int64 table in_off[n_utt+1] | out_off[n_utt+1] |
+ *   tile_off[n_utt+1] | tile_utt[tiles] (3 * (n_utt + 1) + tiles entries), which the caller copies to the device.  An
+ *   empty utterance is DS_ERR_BAD_SHAPE.  DS_ERR_UNSUPPORTED: with T = ceil((2 * half_width + 1) / up) taps per output,
+ *   a polyphase table of more than 16384 entries (up * (T | 1)), or a tile whose input span does not fit the LDS next to
+ *   the table (down / up in the hundreds).
+ * ds_resample_poly_f32: samples f32 (in_int16 = 0) or int16 PCM scaled by 1/32768 (in_int16 = 1), interleaved
+ *   [frames][channels] with 1 <= channels <= 8 (else DS_ERR_UNSUPPORTED): the channels of a frame are summed in order in
+ *   f32 and the sum divided by `channels` in f32 before filtering.  table (device) from ds_resample_plan.  taps (device):
+ *   the table in polyphase form [up][T | 1] f32, row p = the taps of outputs with (half_width + m * down) % up == p in the
+ *   order of ascending input index: entry [p][j] = h[p + (T - 1 - j) * up], zero where that index exceeds 2 * half_width
+ *   and in the padding column.  out [total outputs] f32. */
+int ds_resample_plan(const long long *lengths, int n_utt, int up, int down, int half_width, long long *table,
+                     long long *counts);
+int ds_resample_poly_f32(const void *samples, int in_int16, int channels, const long long *table, int n_utt, int n_tiles,
+                         const float *taps, int up, int down, int half_width, float *out, void *stream);
 
 #ifdef __cplusplus
 }
