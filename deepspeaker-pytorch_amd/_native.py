@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_longlong, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libdeepspeaker_hip.so"
@@ -195,6 +195,13 @@ _SIGNATURES = {
     "ds_fbank_normalize_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "ds_resample_plan": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "ds_resample_poly_f32": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, _P, _P]),
+    "ds_vad_tile_frames": (c_int, []),
+    "ds_vad_plan": (c_int, [_P, c_int, _P, _P]),
+    "ds_vad_workspace_bytes": (c_longlong, [c_int, c_int]),
+    "ds_vad_log_energy_f32": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_double, _P, _P]),
+    "ds_vad_decide": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, c_double, _P, _P, _P, _P, _P]),
+    "ds_vad_scan": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P]),
+    "ds_vad_select_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
 }
 
 

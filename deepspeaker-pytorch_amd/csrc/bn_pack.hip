@@ -417,7 +417,7 @@ extern "C" long long ds_sched_free_slots(void) {
     return (long long)P.free_slots(dev);
 }
 
-extern "C" int ds_version(void) { return 900; }   // 900: polyphase resampler (resample.hip); 800: speaker identification (identify.hip); 700: log-mel filterbank front end (ds_fbank_*); 600: round 6 (caller-owned scheduler workspace, ds_mfma_rate_probe_data); 500: round 5; 400: round 4 (fp16 training step, refinement probes, launch-bound timing); 30x: round-3 ABI (300: split grouped BatchNorm backward for data parallelism, grouped f64 sums; 301: + ds_conv_dgrad_bnbwd_bf16, ds_bn_bwd_group_finish_f32)
+extern "C" int ds_version(void) { return 1000; }   // 1000: energy VAD (vad.hip); 900: polyphase resampler (resample.hip); 800: speaker identification (identify.hip); 700: log-mel filterbank front end (ds_fbank_*); 600: round 6 (caller-owned scheduler workspace, ds_mfma_rate_probe_data); 500: round 5; 400: round 4 (fp16 training step, refinement probes, launch-bound timing); 30x: round-3 ABI (300: split grouped BatchNorm backward for data parallelism, grouped f64 sums; 301: + ds_conv_dgrad_bnbwd_bf16, ds_bn_bwd_group_finish_f32)
 
 // ---- launch timing (see DS_LAUNCH_BIG_LDS in ds_device.h) ----
 extern "C" int ds_event_create(void **out_event) {

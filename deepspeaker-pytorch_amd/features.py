@@ -11,6 +11,10 @@ ready for `data.FeatureStore.from_waveforms`.  Frame counts follow from the host
 Audio at another rate, or with several channels, goes through `resample` first (csrc/resample.hip): the resampling and
 mono down-mix of the reference's `librosa.load(filename, sr=16000, mono=True)` (audio_processing.py:10) as one rational
 polyphase filter with SciPy's `resample_poly` design.  Decoding files stays on the host.
+
+Recordings with silence in them go through an energy voice-activity decision (csrc/vad.hip: `voiced_frames`,
+`select_frames`, the `vad=` keyword of `log_mel_fbank`): only the voiced frames become rows, and the normalisation runs
+over what was kept.
 """
 from __future__ import annotations
 
@@ -230,9 +234,183 @@ def resample(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], orig_rate: 
     return out, out_lens
 
 
+def _fbank_plan(eng, lens: np.ndarray, config: FbankConfig, dev: torch.device):
+    """Framing on the host (the lengths are host data): (table on the device, frame offsets, frames, tiles, rows per
+    tile) of ds_fbank_plan."""
+    n_utt = len(lens)
+    counts = np.zeros(3, np.int64)
+    lens_c = np.ascontiguousarray(lens)
+    plan = lambda table: eng.lib.call("ds_fbank_plan", lens_c.ctypes.data, n_utt, config.frame_len, config.frame_step,
+                                      config.nfft, config.nfilt, None if table is None else table.ctypes.data,
+                                      counts.ctypes.data)
+    plan(None)
+    n_frames, n_tiles, tile_rows = (int(v) for v in counts)
+    table = np.zeros(3 * (n_utt + 1) + n_tiles, np.int64)
+    plan(table)
+    offsets = table[n_utt + 1:2 * (n_utt + 1)].copy()
+    return _upload(table, dev), offsets, n_frames, n_tiles, tile_rows
+
+
+@dataclass(frozen=True)
+class VadConfig:
+    """The energy voice-activity rule (Kaldi's compute-vad-energy on this package's framing, csrc/vad.hip): frame t is
+    voiced iff at least `proportion_threshold` of the frames t - frames_context .. t + frames_context (clipped to the
+    utterance) have a log energy above energy_threshold + energy_mean_scale * (the utterance's mean log energy).  The
+    energy is ln(max(sum (32768 x)^2, energy_floor)) over the raw samples of the frame: the int16 scale, so the usual
+    recipe thresholds carry over."""
+    energy_threshold: float = 5.5
+    energy_mean_scale: float = 0.5
+    frames_context: int = 2
+    proportion_threshold: float = 0.12
+    energy_floor: float = 1.1920929e-07
+
+    def __post_init__(self):
+        for name in ("energy_threshold", "energy_mean_scale", "proportion_threshold", "energy_floor"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        if isinstance(self.frames_context, bool) or not isinstance(self.frames_context, (int, np.integer)) \
+                or self.frames_context < 0:
+            raise ValueError(f"frames_context must be a non-negative integer, got {self.frames_context!r}")
+        if not 0.0 < self.proportion_threshold <= 1.0:
+            raise ValueError(f"proportion_threshold must be in (0, 1], got {self.proportion_threshold!r}")
+        if not self.energy_floor > 0.0:
+            raise ValueError(f"energy_floor must be positive, got {self.energy_floor!r}")
+
+
+SELECT_TILE_ROWS = 64                            # rows per workgroup of the selection and of the normalisation after it
+
+
+def _log_energy(eng, packed, table_dev, n_utt, n_frames, n_tiles, tile_rows, config: FbankConfig, floor: float):
+    out = torch.empty(n_frames, dtype=torch.float32, device=packed.device)
+    eng.lib.call("ds_vad_log_energy_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, eng._p(table_dev), n_utt,
+                 n_tiles, tile_rows, config.frame_len, config.frame_step, float(floor), eng._p(out), eng._stream(out))
+    return out
+
+
+def _vad_plan(eng, offsets: np.ndarray, dev: torch.device):
+    """(decision table on the device, decision tiles) of ds_vad_plan over the host frame offsets."""
+    n_utt = len(offsets) - 1
+    counts = np.zeros(3, np.int64)
+    off_c = np.ascontiguousarray(offsets, np.int64)
+    plan = lambda table: eng.lib.call("ds_vad_plan", off_c.ctypes.data, n_utt, None if table is None else table.ctypes.data,
+                                      counts.ctypes.data)
+    plan(None)
+    n_dtiles = int(counts[1])
+    table = np.zeros(2 * (n_utt + 1) + n_dtiles, np.int64)
+    plan(table)
+    return _upload(table, dev), n_dtiles
+
+
+def _vad_buffers(eng, n_utt, n_frames, n_dtiles, dev):
+    scan = torch.empty(n_frames, dtype=torch.int32, device=dev)
+    kept = torch.empty(n_utt, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(eng.lib.raw("ds_vad_workspace_bytes")(n_utt, n_dtiles)) // 8, dtype=torch.int64, device=dev)
+    return scan, kept, ws
+
+
+def _voiced(eng, packed, lens, vad: VadConfig, config: FbankConfig, plan=None):
+    """(mask, scan, kept, decision table, frame offsets), all but the last on the device; `plan`: the caller's
+    `_fbank_plan` of the same lengths."""
+    dev = packed.device
+    n_utt = len(lens)
+    table_dev, offsets, n_frames, n_tiles, tile_rows = _fbank_plan(eng, lens, config, dev) if plan is None else plan
+    energy = _log_energy(eng, packed, table_dev, n_utt, n_frames, n_tiles, tile_rows, config, vad.energy_floor)
+    vtable_dev, n_dtiles = _vad_plan(eng, offsets, dev)
+    mask = torch.empty(n_frames, dtype=torch.uint8, device=dev)
+    scan, kept, ws = _vad_buffers(eng, n_utt, n_frames, n_dtiles, dev)
+    eng.lib.call("ds_vad_decide", eng._p(energy), eng._p(vtable_dev), n_utt, n_dtiles, float(vad.energy_threshold),
+                 float(vad.energy_mean_scale), int(vad.frames_context), float(vad.proportion_threshold), eng._p(mask),
+                 eng._p(scan), eng._p(kept), eng._p(ws), eng._stream(mask))
+    return mask, scan, kept, vtable_dev, offsets
+
+
+def _select(eng, feats, mask, scan, kept, vtable_dev):
+    """(packed kept rows, new host offsets, table over the kept rows, its tiles, the workspace holding the tiles' sums).
+    Reads `kept` back: the one copy to the host."""
+    dev = feats.device
+    n_utt, nfilt = kept.numel(), feats.shape[1]
+    counts = kept.cpu().numpy()
+    new_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    tiles = -(-counts // SELECT_TILE_ROWS)
+    n_ktiles = int(tiles.sum())
+    out = torch.empty((int(new_off[-1]), nfilt), dtype=torch.float32, device=dev)
+    if n_ktiles == 0:
+        return out, new_off, None, 0, None
+    ktable = np.concatenate([np.zeros(n_utt + 1, np.int64), new_off, [0], np.cumsum(tiles),
+                             np.repeat(np.arange(n_utt, dtype=np.int64), tiles)]).astype(np.int64)
+    ktable_dev = _upload(ktable, dev)
+    ws = torch.empty(int(eng.lib.raw("ds_fbank_workspace_bytes")(n_utt, n_ktiles, nfilt)) // 8, dtype=torch.float64,
+                     device=dev)
+    eng.lib.call("ds_vad_select_f32", eng._p(feats), eng._p(mask), eng._p(scan), eng._p(vtable_dev), eng._p(ktable_dev),
+                 n_utt, n_ktiles, nfilt, SELECT_TILE_ROWS, eng._p(out), eng._p(ws), eng._stream(out))
+    return out, new_off, ktable_dev, n_ktiles, ws
+
+
+def frame_log_energy(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config: FbankConfig = FbankConfig(),
+                     lengths: Optional[Sequence[int]] = None, *, energy_floor: float = VadConfig.energy_floor
+                     ) -> Tuple[torch.Tensor, np.ndarray]:
+    """The log energy of every frame of the filterbank's framing: ln(max(sum (32768 x)^2, energy_floor)) over the raw
+    samples (int16 PCM enters as its integer value), zero past the utterance's end.  `waveforms` / `lengths`: as for
+    `log_mel_fbank`.  Returns the packed float32 [sum T_u] on the device and the host int64 frame offsets [n_utt + 1].
+    Every frame is summed in one fixed order: the values do not depend on the batch."""
+    eng = _eng()
+    packed, lens = _pack(waveforms, lengths)
+    table_dev, offsets, n_frames, n_tiles, tile_rows = _fbank_plan(eng, lens, config, packed.device)
+    return _log_energy(eng, packed, table_dev, len(lens), n_frames, n_tiles, tile_rows, config, energy_floor), offsets
+
+
+def voiced_frames(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], vad: VadConfig = VadConfig(),
+                  config: FbankConfig = FbankConfig(), lengths: Optional[Sequence[int]] = None, *,
+                  orig_rate: Optional[int] = None, channels: int = 1) -> Tuple[torch.Tensor, np.ndarray]:
+    """The voice-activity decision of `VadConfig` for every frame of the filterbank's framing.  `waveforms`, `lengths`,
+    `orig_rate`, `channels`: as for `log_mel_fbank`; audio at another rate is resampled first and the decision is that of
+    the resampled mono signal.  Returns the uint8 mask [sum T_u] (1 = voiced) on the device and the host int64 frame
+    offsets [n_utt + 1]: the rows of `log_mel_fbank(...)[0]`.  Nothing is read back."""
+    if orig_rate is not None or channels != 1:
+        waveforms, lengths = resample(waveforms, config.sample_rate if orig_rate is None else orig_rate,
+                                      config.sample_rate, channels, lengths=lengths)
+    packed, lens = _pack(waveforms, lengths)
+    mask, _, _, _, offsets = _voiced(_eng(), packed, lens, vad, config)
+    return mask, offsets
+
+
+def select_frames(feats: torch.Tensor, offsets: Sequence[int], mask: torch.Tensor) -> Tuple[torch.Tensor, np.ndarray]:
+    """The rows of `feats` [sum T_u, F] float32 whose `mask` entry (uint8 [sum T_u], non-zero = keep) is set, packed in
+    their order, and the new host int64 offsets [n_utt + 1]; an utterance without a kept row has none
+    (offsets[u] == offsets[u + 1]).
+
+    This is the one place of the front end that READS BACK from the device: the n_utt kept counts, in one copy, because
+    offsets are host data throughout this package and the result's size depends on them.  The call therefore waits for
+    the stream and cannot be captured into a graph."""
+    if not isinstance(feats, torch.Tensor) or feats.dim() != 2 or feats.dtype != torch.float32:
+        raise ValueError("feats must be a 2-D float32 tensor")
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 1 or mask.dtype != torch.uint8:
+        raise ValueError("mask must be a 1-D uint8 tensor")
+    off = np.asarray(offsets, np.int64)
+    if off.ndim != 1 or len(off) < 2 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != feats.shape[0]:
+        raise ValueError("offsets must rise from 0 to the number of rows")
+    if mask.numel() != feats.shape[0]:
+        raise ValueError(f"the mask has {mask.numel()} entries for {feats.shape[0]} rows")
+    if mask.device != feats.device:
+        raise ValueError("mask and feats must be on one device")
+    eng = _eng()
+    feats, mask = feats.contiguous(), mask.contiguous()
+    n_utt = len(off) - 1
+    vtable_dev, n_dtiles = _vad_plan(eng, off, feats.device)
+    if n_dtiles == 0:
+        return feats.new_empty((0, feats.shape[1])), np.zeros(n_utt + 1, np.int64)
+    scan, kept, ws = _vad_buffers(eng, n_utt, feats.shape[0], n_dtiles, feats.device)
+    eng.lib.call("ds_vad_scan", eng._p(mask), eng._p(vtable_dev), n_utt, n_dtiles, eng._p(scan), eng._p(kept), eng._p(ws),
+                 eng._stream(mask))
+    out, new_off, _, _, _ = _select(eng, feats, mask, scan, kept, vtable_dev)
+    return out, new_off
+
+
 def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config: FbankConfig = FbankConfig(),
                   normalize: Optional[str] = "mean", lengths: Optional[Sequence[int]] = None, *,
-                  orig_rate: Optional[int] = None, channels: int = 1) -> Tuple[torch.Tensor, np.ndarray]:
+                  orig_rate: Optional[int] = None, channels: int = 1, vad: Optional[VadConfig] = None
+                  ) -> Tuple[torch.Tensor, np.ndarray]:
     """mk_MFB of every waveform in one call chain on the waveforms' device.
 
     `waveforms`: a sequence of 1-D tensors (float32 samples, or int16 PCM, which is scaled by 1/32768), or ONE packed
@@ -241,11 +419,16 @@ def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config
     `orig_rate` / `channels`: the waveforms' own sample rate and interleaved channel count; given, they are first
     resampled to config.sample_rate and mixed down to mono on the device (`resample`), which together with this
     function is the reference's librosa.load(..., sr=16000, mono=True) followed by mk_MFB.
+    `vad`: given, only the voiced frames of `voiced_frames` (decided on the same, resampled, waveform) are kept, in
+    order, and the normalisation runs over the kept rows; an utterance without a voiced frame has no row.  This reads the
+    kept counts back (`select_frames`), so the call waits for the stream and cannot be captured into a graph.
     Returns the packed [sum T_u, nfilt] float32 features on the device and the host int64 frame offsets [n_utt + 1]:
     utterance u is rows offsets[u]:offsets[u+1].  Decoding files is the caller's; deltas are not computed (the
     reference's USE_DELTA is False)."""
     if normalize not in _NORMALIZE:
         raise ValueError(f"normalize must be one of {_NORMALIZE}, got {normalize!r}")
+    if vad is not None and not isinstance(vad, VadConfig):
+        raise ValueError(f"vad must be a VadConfig or None, got {vad!r}")
     if orig_rate is not None or channels != 1:
         waveforms, lengths = resample(waveforms, config.sample_rate if orig_rate is None else orig_rate,
                                       config.sample_rate, channels, lengths=lengths)
@@ -254,18 +437,7 @@ def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config
     dev = packed.device
     n_utt = len(lens)
     fl, fs, nfft, nfilt = config.frame_len, config.frame_step, config.nfft, config.nfilt
-
-    # framing on the host (the lengths are host data): frame counts, offsets and the tile table
-    counts = np.zeros(3, np.int64)
-    lens_c = np.ascontiguousarray(lens)
-    plan = lambda table: eng.lib.call("ds_fbank_plan", lens_c.ctypes.data, n_utt, fl, fs, nfft, nfilt,
-                                      None if table is None else table.ctypes.data, counts.ctypes.data)
-    plan(None)
-    n_frames, n_tiles, tile_rows = (int(v) for v in counts)
-    table = np.zeros(3 * (n_utt + 1) + n_tiles, np.int64)
-    plan(table)
-    offsets = table[n_utt + 1:2 * (n_utt + 1)].copy()
-    table_dev = _upload(table, dev)
+    table_dev, offsets, n_frames, n_tiles, tile_rows = _fbank_plan(eng, lens, config, dev)
 
     basis, band, weights, wstride = _device_tables(config, dev)
     out = torch.empty((n_frames, nfilt), dtype=torch.float32, device=dev)
@@ -275,6 +447,14 @@ def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config
     eng.lib.call("ds_fbank_logmel_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, eng._p(table_dev),
                  n_utt, n_tiles, eng._p(basis), eng._p(band), eng._p(weights), wstride, fl, fs, nfft, nfilt,
                  1 if config.use_logscale else 0, eng._p(out), eng._p(workspace), stream)
+    if vad is not None:
+        # the kept rows, their tiles' sums and the table over them: the normalisation below runs over what was kept
+        mask, scan, kept, vtable_dev, _ = _voiced(eng, packed, lens, vad, config,
+                                                  (table_dev, offsets, n_frames, n_tiles, tile_rows))
+        out, offsets, table_dev, n_tiles, workspace = _select(eng, out, mask, scan, kept, vtable_dev)
+        tile_rows = SELECT_TILE_ROWS
+        if n_tiles == 0:
+            return out, offsets
     if normalize is not None:
         eng.lib.call("ds_fbank_normalize_f32", eng._p(out), eng._p(table_dev), n_utt, n_tiles, nfilt, tile_rows,
                      1 if normalize == "mean_std" else 0, eng._p(workspace), stream)

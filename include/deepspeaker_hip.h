@@ -88,7 +88,7 @@ int ds_version(void);            /* 100: round 1; 200: round 2 (fp16 path, group
                                     near-tie refinement, launch-bound timing); 500: round 5; 600: round 6 (caller-owned
                                     scheduler workspace); 700: log-mel filterbank front end (ds_fbank_*); 800: speaker identification
                                     (ds_nearest_*, ds_segment_mean_rows_f32, ds_rank_hits_i32); 900: polyphase resampler
-                                    (ds_resample_plan, ds_resample_poly_f32) */
+                                    (ds_resample_plan, ds_resample_poly_f32); 1000: energy VAD (ds_vad_*) */
 /* launch timing without marker packets: the next MFMA convolution / filter-gradient launch of the calling thread
  * records its own execution into the armed pair (hipExtLaunchKernelGGL); ds_launch_timing_end() disarms and returns
  * how many such launches happened since arming (1 = the timed call was a single kernel) */
@@ -725,6 +725,52 @@ int ds_resample_plan(const long long *lengths, int n_utt, int up, int down, int 
                      long long *counts);
 int ds_resample_poly_f32(const void *samples, int in_int16, int channels, const long long *table, int n_utt, int n_tiles,
                          const float *taps, int up, int down, int half_width, float *out, void *stream);
+
+/* ---- energy voice-activity decision and selection of the voiced frames (csrc/vad.hip), on the filterbank's framing ----
+ * The rule (Kaldi's compute-vad-energy / select-voiced-frames, not bit-compatible with it), for an utterance of T frames:
+ *   e[t]   = ln(max(sum_i (32768 x[t * frame_step + i])^2, energy_floor)), 0 <= i < frame_len: raw samples (no
+ *            pre-emphasis, window or DC removal), zero past the utterance's end; int16 enters as its integer value
+ *   thr    = energy_threshold + energy_mean_scale * mean_t e[t]      (f64, accumulated in a fixed order, no atomics)
+ *   voiced = count(e[lo..hi] > thr) >= proportion_threshold * (hi - lo + 1), lo = max(0, t - frames_context),
+ *            hi = min(T - 1, t + frames_context): the window is clipped to the utterance
+ * Every frame is summed in one fixed order: deterministic, independent of tile, batch and call.  Every buffer is the
+ * caller's; nothing is allocated or synchronised.
+ * ds_vad_log_energy_f32: samples as for ds_fbank_logmel_f32, table (device) and tile_rows (counts[2]) from ds_fbank_plan;
+ *   out [total frames] f32.  The frames at the floor hold (float)log(energy_floor) exactly.  energy_floor not a positive
+ *   finite float, frame_len or frame_step < 1: DS_ERR_BAD_SHAPE; a tile whose samples do not fit the LDS:
+ *   DS_ERR_UNSUPPORTED.
+ * ds_vad_tile_frames: frames per workgroup of the decision kernels.
+ * ds_vad_plan (HOST): from the host frame offsets frame_off[n_utt + 1] (an utterance may have no frame).  With
+ *   table == NULL only counts[3] = {total frames, decision tiles, frames per tile} is written; otherwise also the int64
+ *   table frame_off[n_utt+1] | dtile_off[n_utt+1] | dtile_utt[tiles] (2 * (n_utt + 1) + tiles entries), which the caller
+ *   copies to the device.  Tiles never straddle utterances.  Offsets that decrease, or 2^31 frames in one utterance:
+ *   DS_ERR_BAD_SHAPE.
+ * ds_vad_workspace_bytes: the workspace of ds_vad_decide / ds_vad_scan: thresholds f64 [n_utt], tile counts int64 [tiles].
+ * ds_vad_decide: energy [frames] f32 -> mask [frames] uint8 (1 = voiced), scan [frames] int32 (the exclusive scan of the
+ *   mask INSIDE each utterance) and kept [n_utt] int64.  Four launches: thresholds, vote + tile counts, scan of the
+ *   tile counts per utterance, scan inside the tiles -- an utterance may span any number of workgroups and none waits
+ *   for another.  frames_context < 0, proportion_threshold outside (0, 1] or a non-finite parameter: DS_ERR_BAD_SHAPE;
+ *   frames_context > 64: DS_ERR_UNSUPPORTED.
+ * ds_vad_scan: scan and kept of a caller's own mask (non-zero = kept).
+ * ds_vad_select_f32: the kept rows of feat [frames][nfilt] f32, in order, packed into out [sum kept][nfilt].  ktable
+ *   (device): the ds_fbank_plan layout over the KEPT frames -- samp_off (not read) | frame_off | tile_off | tile_utt with
+ *   tile_rows rows per tile, an utterance without kept frames without tiles -- built by the caller from `kept`.
+ *   workspace: ds_fbank_workspace_bytes(n_utt, n_ktiles, nfilt); its per-tile {sum, sum of squares} [n_ktiles][2][nfilt]
+ *   f64 over the kept rows are written in ds_fbank_logmel_f32's layout and order, so ds_fbank_normalize_f32 with ktable
+ *   normalises over the kept rows. */
+int ds_vad_tile_frames(void);
+int ds_vad_plan(const long long *frame_off, int n_utt, long long *table, long long *counts);
+long long ds_vad_workspace_bytes(int n_utt, int n_dtiles);
+int ds_vad_log_energy_f32(const void *samples, int in_int16, const long long *table, int n_utt, int n_tiles, int tile_rows,
+                          int frame_len, int frame_step, double energy_floor, float *out, void *stream);
+int ds_vad_decide(const float *energy, const long long *vtable, int n_utt, int n_dtiles, double energy_threshold,
+                  double energy_mean_scale, int frames_context, double proportion_threshold, unsigned char *mask, int *scan,
+                  long long *kept, void *workspace, void *stream);
+int ds_vad_scan(const unsigned char *mask, const long long *vtable, int n_utt, int n_dtiles, int *scan, long long *kept,
+                void *workspace, void *stream);
+int ds_vad_select_f32(const float *feat, const unsigned char *mask, const int *scan, const long long *vtable,
+                      const long long *ktable, int n_utt, int n_ktiles, int nfilt, int tile_rows, float *out,
+                      double *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,400 @@
+"""TEST INFRASTRUCTURE: the cases of the energy voice-activity decision and the selection of voiced frames (csrc/vad.hip,
+features.frame_log_energy / voiced_frames / select_frames, the vad= keyword of log_mel_fbank and
+FeatureStore.from_waveforms), written once and run by tests/test_emul_vad.py through the host emulator and by
+tests/test_gpu_vad.py on the device.  Every body takes a `Ctx`: the features module to call, the device the tensors live
+on and the loaded library.  References come from tests/vad_reference.py (float64) and are computed once per process."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import fbank_reference as FR
+import resample_bodies as RB
+import vad_reference as V
+from resample_bodies import Ctx                                  # noqa: F401  (the same context)
+
+FL, FS, CTX = 400, 160, V.DEFAULTS["frames_context"]
+DTYPES = ("float32", "int16")
+PLAIN = {"silence": False, "noise": True, "dc": True, "tone": True}      # kind -> every frame voiced?
+KINDS = ("gated", "ramp") + tuple(PLAIN)
+
+# |log energy - restatement|, a priori.  A frame's sum is frame_len squares (one rounding each) added in f32 (at most
+# frame_len - 1 roundings on any one path, every term non-negative): a relative error of at most (frame_len + 1) * 2^-24
+# in the sum, in whatever order, and the same absolute error in its logarithm (|ln(1 + d)| <= 1.0001 |d| here).  logf is
+# good to a few ulp, taken as 4 here, and |e| < 32 (the floor is ln 2^-23 = -15.9, a full-scale frame ln(400 * 2^30) =
+# 26.8), where an ulp is at most 2^-19.  Together 3.2e-5 at frame_len = 400.
+# Measured worst case over every kind, length and dtype below: host emulator 1.1e-6 ("noise" int16; the host's logf is
+# correctly rounded to within an ulp), MI355X 4.1e-6 ("noise" int16 and "gated" int16; two ulp of the device's logf at
+# |e| >= 16); the frames at the floor ("silence") are exact on both.
+ENERGY_TOL = 1.0001 * (FL + 1) * 2.0 ** -24 + 4 * 2.0 ** -19
+# a decision may differ only where some frame of the window has an energy this close to its threshold: the energy's own
+# band plus the threshold's (|energy_mean_scale| times the mean's error, itself at most ENERGY_TOL)
+BAND = ENERGY_TOL * (1.0 + abs(V.DEFAULTS["energy_mean_scale"]))
+TOL_DB = 5e-4                                    # the filterbank's own bar (tests/test_gpu_fbank.py), same arithmetic
+
+
+def tile_frames(lib):
+    return int(lib.raw("ds_vad_tile_frames")())
+
+
+def samples_for(T):
+    """a length that gives T frames, the last one partly zero padding"""
+    return FL // 2 if T == 1 else FL + (T - 1) * FS - 37
+
+
+def lengths(tile):
+    ns = [1, 399, 400, 401, 560, 561]
+    for T in (CTX, CTX + 1, 2 * CTX + 1, 63, 64, 65, 129, tile - 1, tile, tile + 1, 2 * tile + 1):
+        ns.append(samples_for(T))
+    return ns
+
+
+def _speech(seed, n):
+    rs = np.random.RandomState(seed)
+    return rs, FR.synthetic_audio(seed, n, kind="ar").astype(np.float64), 1e-3 * rs.randn(n)
+
+
+def gated(seed, n):
+    """speech-like bursts of 2000 .. 8000 samples with gaps of 1500 .. 6000 over a noise floor"""
+    rs, sp, bg = _speech(seed, n)
+    g = np.zeros(n)
+    p = int(rs.randint(0, 3000))
+    while p < n:
+        b = int(rs.randint(2000, 8000))
+        g[p:p + b] = 1.0
+        p += b + int(rs.randint(1500, 6000))
+    return (sp * g + bg).astype(np.float32)
+
+
+def ramp(seed, n):
+    """the same speech-like signal fading linearly from full level into the noise floor"""
+    _, sp, bg = _speech(seed, n)
+    return (sp * np.linspace(1.0, 0.0, n) + bg).astype(np.float32)
+
+
+def signal(kind, seed, n):
+    if kind == "gated":
+        return gated(seed, n)
+    if kind == "ramp":
+        return ramp(seed, n)
+    return FR.synthetic_audio(seed, n, kind=kind)
+
+
+@functools.lru_cache(maxsize=None)
+def _float_signals(kind, tile):
+    # (the seeds: a "noise" utterance of ONE sample is voiced only if that sample is not a small one, |x| > 0.0075;
+    # decisions() asserts on the reference side that these inputs are what the case assumes)
+    return [signal(kind, 4001 + 100 * KINDS.index(kind) + i, n) for i, n in enumerate(lengths(tile))]
+
+
+@functools.lru_cache(maxsize=None)
+def batch(kind, dtype, tile):
+    """(signals, float64 energies, thresholds, reference masks) of every length, read-only"""
+    xs = [FR.int16_quantised(x) if dtype == "int16" else x for x in _float_signals(kind, tile)]
+    es = [V.log_energy(x) for x in xs]
+    thrs = [V.threshold(e) for e in es]
+    masks = [V.decide(e) for e in es]
+    for a in xs + es + masks:
+        a.setflags(write=False)
+    return xs, es, thrs, masks
+
+
+def split(t, off):
+    a = t.cpu().numpy()
+    assert len(a) == off[-1]
+    return [a[off[u]:off[u + 1]] for u in range(len(off) - 1)]
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def exempt_frames(e, thr, ctx=CTX, band=BAND):
+    """frames whose clipped window holds a frame within `band` of the threshold"""
+    near = np.abs(e - thr) < band
+    T = len(e)
+    return np.array([near[max(0, t - ctx):min(T - 1, t + ctx) + 1].any() for t in range(T)])
+
+
+# ---- 1. energy values ----
+def energy_values(ctx, kind, dtype):
+    tile = tile_frames(ctx.lib)
+    xs, es, _, _ = batch(kind, dtype, tile)
+    out, off = ctx.features.frame_log_energy([ctx.t(x) for x in xs])
+    assert out.dtype == torch.float32 and out.dim() == 1 and off.dtype == np.int64
+    assert np.diff(off).tolist() == [len(e) for e in es] == [FR.n_frames(len(x), FL, FS) for x in xs]
+    assert {1, 2, 3, CTX, CTX + 1, 2 * CTX + 1, 63, 64, 65, 129, tile - 1, tile, tile + 1, 2 * tile + 1} <= set(np.diff(off))
+    got = split(out, off)
+    err = max(float(np.abs(g - e).max()) for g, e in zip(got, es))
+    print(f"log energy {kind} {dtype}: max abs error {err:.3e}, bound {ENERGY_TOL:.3e}")
+    assert err <= ENERGY_TOL, (err, ENERGY_TOL)
+    assert max(float(np.abs(e).max()) for e in es) < 32.0            # the range the bound was derived for
+    if kind == "silence":                                            # at the floor: the floor's own logarithm, exactly
+        for g, e in zip(got, es):
+            np.testing.assert_array_equal(bits(g), bits(e.astype(np.float32)))
+
+
+# ---- 2. decisions ----
+def decisions(ctx, kind, dtype):
+    tile = tile_frames(ctx.lib)
+    xs, es, thrs, masks = batch(kind, dtype, tile)
+    # the reference side first: the inputs must leave (next to) nothing to the band
+    exempt = [exempt_frames(e, thr) for e, thr in zip(es, thrs)]
+    n_exempt, n_all = sum(int(x.sum()) for x in exempt), sum(len(x) for x in exempt)
+    assert n_exempt <= 0.01 * n_all, (kind, n_exempt, n_all)
+    if kind != "ramp":
+        assert n_exempt == 0, (kind, n_exempt)
+    if kind in PLAIN:
+        assert all(bool((m == PLAIN[kind]).all()) for m in masks), kind
+    else:
+        long_ones = np.concatenate([m for m in masks if len(m) >= 63])
+        assert 0.02 < long_ones.mean() < 0.98, (kind, long_ones.mean())   # both decisions occur
+    mask, off = ctx.features.voiced_frames([ctx.t(x) for x in xs])
+    assert mask.dtype == torch.uint8 and mask.dim() == 1 and np.diff(off).tolist() == [len(m) for m in masks]
+    bad = 0
+    for g, m, x in zip(split(mask, off), masks, exempt):
+        assert set(np.unique(g).tolist()) <= {0, 1}
+        bad += int(((g != 0) != m)[~x].sum())
+    print(f"decisions {kind} {dtype}: {n_all} frames, {n_exempt} exempt, {bad} wrong, "
+          f"{sum(int(m.sum()) for m in masks) / n_all:.1%} voiced")
+    assert bad == 0
+
+
+# ---- 3. clipping and isolation ----
+def _one_loud_frame(T, last):
+    x = np.zeros(FL + (T - 1) * FS, np.float32)
+    rs = np.random.RandomState(T)
+    if last:
+        x[(T - 1) * FS + FL - FS:] = 0.5 * np.sign(rs.randn(FS))     # samples only frame T - 1 covers
+    else:
+        x[:FS] = 0.5 * np.sign(rs.randn(FS))                         # samples only frame 0 covers
+    return x
+
+
+def clipping(ctx):
+    F = ctx.features
+    T = 20
+    loud = FR.synthetic_audio(1, 8000, kind="tone")
+    first, last = _one_loud_frame(T, False), _one_loud_frame(T, True)
+    silent, short = np.zeros(FL + 39 * FS, np.float32), np.zeros(FL + FS, np.float32)
+    xs = [loud, first, loud, last, loud, silent, loud, short, loud]
+    for cfg, reach in ((F.VadConfig(), CTX), (F.VadConfig(proportion_threshold=0.3), 0)):
+        # default: one frame of 3, 4 or 5 is enough (0.12); at 0.3 only the window of 3 at the very edge is: the loud
+        # frame itself votes yes, its neighbours (windows of 4 and 5 need 2) do not
+        mask, off = F.voiced_frames([ctx.t(x) for x in xs], cfg)
+        ms = split(mask, off)
+        want_first, want_last = np.zeros(T, np.uint8), np.zeros(T, np.uint8)
+        want_first[:reach + 1] = 1
+        want_last[T - 1 - reach:] = 1
+        kw = dict(proportion_threshold=cfg.proportion_threshold)
+        assert V.vad(first, **kw).tolist() == want_first.astype(bool).tolist()         # the restatement agrees
+        assert V.vad(last, **kw).tolist() == want_last.astype(bool).tolist()
+        assert ms[1].tolist() == want_first.tolist() and ms[3].tolist() == want_last.tolist()
+        assert all(m.all() for m in ms[0::2])                        # the loud neighbours
+        assert not ms[5].any() and len(ms[5]) == 40 and not ms[7].any() and len(ms[7]) == 2
+        feats = ctx.t(np.arange(off[-1] * 4, dtype=np.float32).reshape(-1, 4))
+        kept, new_off = F.select_frames(feats, off, mask)
+        assert np.diff(new_off).tolist() == [int(m.sum()) for m in ms]
+        assert new_off[6] == new_off[5] and new_off[8] == new_off[7] and kept.shape[0] == new_off[-1]
+
+
+# ---- 4. selection ----
+@functools.lru_cache(maxsize=None)
+def selection_signals():
+    """zero-row utterances first, in the middle and last; the others around the fbank tile"""
+    quiet = lambda n: np.zeros(n, np.float32)
+    xs = [quiet(1000)] + [gated(600 + i, samples_for(T)) for i, T in enumerate((1, 3, 63, 64))] + [quiet(401)] + \
+         [gated(610 + i, samples_for(T)) for i, T in enumerate((65, 129))] + [quiet(1)]
+    for x in xs:
+        x.setflags(write=False)
+    return xs
+
+
+def selection(ctx):
+    F = ctx.features
+    xs = [ctx.t(x) for x in selection_signals()]
+    feats, off = F.log_mel_fbank(xs, normalize=None)
+    mask, off_m = F.voiced_frames(xs)
+    assert off.tolist() == off_m.tolist()
+    out, new_off = F.select_frames(feats, off, mask)
+    m = mask.cpu().numpy().astype(bool)
+    np.testing.assert_array_equal(bits(out.cpu().numpy()), bits(feats.cpu().numpy()[m]))      # values and order
+    counts = [int(m[off[u]:off[u + 1]].sum()) for u in range(len(xs))]
+    assert new_off.dtype == np.int64 and new_off.tolist() == np.concatenate([[0], np.cumsum(counts)]).tolist()
+    assert counts[0] == counts[5] == counts[-1] == 0 and sum(counts) > 100
+    # every length, a narrow matrix whose entries name their row: utterances that span several decision tiles
+    tile = tile_frames(ctx.lib)
+    sig, _, _, masks = batch("gated", "float32", tile)
+    mask, off = F.voiced_frames([ctx.t(x) for x in sig])
+    rows = np.arange(off[-1] * 8, dtype=np.float32).reshape(-1, 8)
+    out, new_off = F.select_frames(ctx.t(rows), off, mask)
+    m = mask.cpu().numpy().astype(bool)
+    np.testing.assert_array_equal(out.cpu().numpy(), rows[m])
+    assert np.diff(new_off).tolist() == [int(m[off[u]:off[u + 1]].sum()) for u in range(len(sig))]
+    # a mask of the caller's own: any non-zero byte keeps the row
+    own = np.random.RandomState(3).randint(0, 3, off[-1]).astype(np.uint8) * 127
+    out, new_off = F.select_frames(ctx.t(rows), off, ctx.t(own))
+    np.testing.assert_array_equal(out.cpu().numpy(), rows[own != 0])
+    # an utterance of more decision tiles than a workgroup has threads (each thread then scans a run of tile counts),
+    # between two short ones
+    long_off = np.array([0, 3, 3 + 2 * 256 * tile + 77, 2 * 256 * tile + 90], np.int64)
+    long_rows = np.arange(long_off[-1] * 4, dtype=np.float32).reshape(-1, 4)
+    long_mask = (np.random.RandomState(4).rand(long_off[-1]) < 0.3).astype(np.uint8)
+    out, new_off = F.select_frames(ctx.t(long_rows), long_off, ctx.t(long_mask))
+    np.testing.assert_array_equal(out.cpu().numpy(), long_rows[long_mask != 0])
+    assert np.diff(new_off).tolist() == [int(long_mask[long_off[u]:long_off[u + 1]].sum()) for u in range(3)]
+    none, zero_off = F.select_frames(ctx.t(rows), off, ctx.t(np.zeros(off[-1], np.uint8)))
+    assert none.shape == (0, 8) and not zero_off.any() and len(zero_off) == len(off)
+
+
+# ---- 5. normalisation over the kept rows ----
+@functools.lru_cache(maxsize=None)
+def normalisation_case():
+    xs = [gated(700, 16000), gated(701, 48000), np.zeros(3000, np.float32), gated(702, 5000),
+          FR.synthetic_audio(703, 561, kind="noise"), FR.synthetic_audio(704, 400, kind="tone"),
+          FR.int16_quantised(gated(705, 16000))]
+    masks = [V.vad(x) for x in xs]
+    raw = [FR.fbank(x.astype(np.float32) / np.float32(32768) if x.dtype == np.int16 else x)[m] for x, m in zip(xs, masks)]
+    # the inputs leave nothing to the band, so the reference mask IS the mask
+    assert not any(exempt_frames(V.log_energy(x), V.threshold(V.log_energy(x))).any() for x in xs)
+    assert [len(r) for r in raw][2] == 0 and min(len(r) for i, r in enumerate(raw) if i != 2) >= 1
+    for a in xs + raw:
+        a.setflags(write=False)
+    return xs, raw
+
+
+def normalisation(ctx, normalize):
+    F = ctx.features
+    xs, raw = normalisation_case()
+    worst = 0.0
+    for sel in (slice(0, 6), slice(6, 7)):                           # the float32 utterances, then the int16 one
+        out, off = F.log_mel_fbank([ctx.t(x) for x in xs[sel]], normalize=normalize, vad=F.VadConfig())
+        assert np.diff(off).tolist() == [len(r) for r in raw[sel]] and out.shape == (off[-1], 64)
+        for g, r in zip(split(out, off), raw[sel]):
+            if len(r):
+                ref = r if normalize is None else FR.normalize_frames(r, scale=normalize == "mean_std")
+                worst = max(worst, float(np.abs(g - ref).max()))
+    print(f"fbank over voiced frames, normalize={normalize}: max abs error {worst:.3e}")
+    assert worst <= TOL_DB, worst
+
+
+def vad_none_is_unchanged(ctx):
+    F = ctx.features
+    x16 = [FR.synthetic_audio(60 + i, n, kind="ar") for i, n in enumerate((401, 5000))]
+    a, off_a = F.log_mel_fbank([ctx.t(v) for v in x16], vad=None)
+    b, off_b = RB.direct_log_mel(ctx, ctx.t(np.concatenate(x16)), [401, 5000])
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and off_a.tolist() == off_b.tolist()
+
+
+# ---- 6. deterministic and batch-invariant ----
+def deterministic(ctx, n_max=30000):
+    F = ctx.features
+    rs = np.random.RandomState(9)
+    xs = [ctx.t(gated(800 + i, int(rs.randint(1, n_max)))) for i in range(20)]
+    mask, off = F.voiced_frames(xs)
+    mask2, _ = F.voiced_frames(xs)
+    e, _ = F.frame_log_energy(xs)
+    e2, _ = F.frame_log_energy(xs)
+    assert torch.equal(mask, mask2) and torch.equal(e.view(torch.int32), e2.view(torch.int32))
+    a, koff = F.log_mel_fbank(xs, normalize="mean_std", vad=F.VadConfig())
+    b, koff2 = F.log_mel_fbank(xs, normalize="mean_std", vad=F.VadConfig())
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and koff.tolist() == koff2.tolist()
+    for u in (0, 7, 19):
+        m1, o1 = F.voiced_frames([xs[u]])
+        e1, _ = F.frame_log_energy([xs[u]])
+        assert o1.tolist() == [0, off[u + 1] - off[u]]
+        assert torch.equal(m1, mask[off[u]:off[u + 1]]) and torch.equal(e1.view(torch.int32), e[off[u]:off[u + 1]].view(torch.int32))
+        a1, k1 = F.log_mel_fbank([xs[u]], normalize="mean_std", vad=F.VadConfig())
+        assert k1.tolist() == [0, koff[u + 1] - koff[u]]
+        assert torch.equal(a1.view(torch.int32), a[koff[u]:koff[u + 1]].view(torch.int32)), u
+    lens = [len(x) for x in xs]
+    mp, op = F.voiced_frames(torch.cat(xs), lengths=lens)
+    ap, kp = F.log_mel_fbank(torch.cat(xs), normalize="mean_std", lengths=lens, vad=F.VadConfig())
+    assert torch.equal(mp, mask) and op.tolist() == off.tolist()
+    assert torch.equal(ap.view(torch.int32), a.view(torch.int32)) and kp.tolist() == koff.tolist()
+
+
+# ---- 7. plumbing ----
+def plumbing(ctx):
+    from deepspeaker_pytorch_amd import data
+    F = ctx.features
+    vad = F.VadConfig()
+    xs = [ctx.t(x) for x in (gated(900, 9000), np.zeros(2000, np.float32), gated(901, 4000))]
+    a, off = F.log_mel_fbank(xs, vad=vad)
+    store = data.FeatureStore.from_waveforms(xs, vad=vad)
+    assert torch.equal(store.features.view(torch.int32), a.view(torch.int32)) and store.offsets.tolist() == off.tolist()
+    assert len(store) == 3 and store.length(1) == 0 and store.length(0) == off[1] > 0
+    crops = store.crops([1, 0, 1], [0, 0, 5], 16)
+    assert crops.shape == (3, 1, 16, 64) and not crops[0].any() and not crops[2].any() and crops[1].any()
+    # another rate, two channels: the decision is that of the resampled mono signal
+    g48 = np.repeat(gated(902, 8000), 3)                             # 48 kHz, crudely: the gating survives
+    stereo = ctx.t(np.stack([g48, 0.5 * g48], 1).reshape(-1).astype(np.float32))
+    m, off_m = F.voiced_frames([stereo], vad, orig_rate=48000, channels=2)
+    mono, lens = F.resample([stereo], 48000, channels=2)
+    m2, off_2 = F.voiced_frames(mono, vad, lengths=lens)
+    assert torch.equal(m, m2) and off_m.tolist() == off_2.tolist() and 0 < int(m.sum()) < m.numel()
+    b, off_b = F.log_mel_fbank([stereo], orig_rate=48000, channels=2, vad=vad)
+    c, off_c = F.log_mel_fbank(mono, lengths=lens, vad=vad)
+    assert torch.equal(b.view(torch.int32), c.view(torch.int32)) and off_b.tolist() == off_c.tolist() == [0, int(m.sum())]
+
+
+# ---- 8. errors ----
+def abi_errors(ctx):
+    lib = ctx.lib
+    p = np.zeros(8, np.int64).ctypes.data                            # a placeholder: validation touches no buffer
+    counts = np.zeros(3, np.int64)
+    off = np.array([0, 5, 5, 2000], np.int64)
+    plan = lib.raw("ds_vad_plan")
+    assert plan(None, 3, None, counts.ctypes.data) == -3 and plan(off.ctypes.data, 0, None, counts.ctypes.data) == -1
+    assert plan(np.array([0, 5, 4], np.int64).ctypes.data, 2, None, counts.ctypes.data) == -1         # falling offsets
+    tile = tile_frames(lib)
+    assert plan(off.ctypes.data, 3, None, counts.ctypes.data) == 0 and counts.tolist() == [2000, 1 + -(-1995 // tile), tile]
+    assert lib.raw("ds_vad_workspace_bytes")(0, 1) == -1 and lib.raw("ds_vad_workspace_bytes")(3, 4) == 56
+    energy = lib.raw("ds_vad_log_energy_f32")
+    assert energy(None, 0, p, 1, 1, 64, 400, 160, 1e-7, p, None) == -3
+    assert energy(p, 0, p, 0, 1, 64, 400, 160, 1e-7, p, None) == -1
+    assert energy(p, 2, p, 1, 1, 64, 400, 160, 1e-7, p, None) == -4          # neither f32 nor int16
+    assert energy(p, 0, p, 1, 1, 64, 400, 160, 0.0, p, None) == -1           # no floor
+    assert energy(p, 0, p, 1, 1, 64, 400, 160, float("nan"), p, None) == -1
+    assert energy(p, 0, p, 1, 1, 64, 400, 1000, 1e-7, p, None) == -4         # a tile's samples do not fit the LDS
+    decide = lambda n_utt=1, n_tiles=1, thr=5.5, scale=0.5, context=2, prop=0.12, e=p, out=p: lib.raw("ds_vad_decide")(
+        e, p, n_utt, n_tiles, thr, scale, context, prop, out, p, p, p, None)
+    assert decide(e=None) == -3 and decide(out=None) == -3
+    assert decide(n_utt=0) == -1 and decide(n_tiles=0) == -1
+    assert decide(context=-1) == -1 and decide(context=65) == -4
+    assert decide(prop=0.0) == -1 and decide(prop=1.5) == -1 and decide(prop=float("nan")) == -1
+    assert decide(thr=float("inf")) == -1 and decide(scale=float("nan")) == -1
+    scan = lib.raw("ds_vad_scan")
+    assert scan(None, p, 1, 1, p, p, p, None) == -3 and scan(p, p, 0, 1, p, p, p, None) == -1
+    select = lib.raw("ds_vad_select_f32")
+    assert select(None, p, p, p, p, 1, 1, 64, 64, p, p, None) == -3
+    assert select(p, p, p, p, p, 0, 1, 64, 64, p, p, None) == -1 and select(p, p, p, p, p, 1, 1, 64, 48, p, p, None) == -1
+    assert select(p, p, p, p, p, 1, 1, 6, 64, p, p, None) == -4              # rows of 6 floats
+
+
+def python_errors(ctx):
+    F = ctx.features
+    for bad in (dict(frames_context=-1), dict(proportion_threshold=0.0), dict(proportion_threshold=1.01),
+                dict(energy_threshold=float("nan")), dict(energy_mean_scale=float("inf")), dict(energy_floor=0.0),
+                dict(frames_context=1.5)):
+        with pytest.raises(ValueError):
+            F.VadConfig(**bad)
+    assert F.VadConfig(proportion_threshold=1.0).frames_context == 2
+    with pytest.raises(Exception):
+        F.VadConfig().frames_context = 3                             # frozen
+    x = ctx.t(gated(1, 3000))
+    feats, off = F.log_mel_fbank([x], normalize=None)
+    mask, _ = F.voiced_frames([x])
+    with pytest.raises(ValueError):
+        F.select_frames(feats, off, mask[:-1])
+    with pytest.raises(ValueError):
+        F.select_frames(feats, off, mask.to(torch.int32))
+    with pytest.raises(ValueError):
+        F.select_frames(feats.double(), off, mask)
+    with pytest.raises(ValueError):
+        F.select_frames(feats, [0, 3], mask)
+    with pytest.raises(ValueError):
+        F.log_mel_fbank([x], vad=True)
+    with pytest.raises(ValueError):
+        F.voiced_frames([ctx.t(np.zeros(100, np.float64))])
