@@ -17,108 +17,57 @@ from ._native import ConvShape
 from .engine import ALPHA, L2_EPS, STAGE_CHANNELS, Engine, PackedWeights, SavedForward
 
 
-def _bn_bwd_group(eng: Engine, g1, g2, act, z, stats, gamma, reducer=None):
-    """_bn_bwd over a batch made of len(stats) members with their own batch statistics (the three forwards of a
-    triplet step run as one batch, Engine.forward_train_group): the reductions run per member on slices of the
-    batch; with a `reducer` the sums of ALL members travel in one all-reduce.  dgamma / dbeta are summed over the
-    members (the reference accumulates them over its three backward passes)."""
-    G = len(stats)
+def _stats_table(stats, c: int):
+    """(G, mean table, invstd table): the members' mean / invstd as consecutive rows of one [G][C] table each.  The
+    statistics of one member (a tuple) are a table of one row; a list of members whose rows already lie consecutively
+    (Engine.forward_train_group lays them out so) is used in place; any other list is stacked first."""
+    members = stats if isinstance(stats, list) else [stats]
+    G, step = len(members), c * 4
+    if all(m_[k].data_ptr() == members[0][k].data_ptr() + g * step for g, m_ in enumerate(members) for k in (0, 1)):
+        return G, members[0][0], members[0][1]
+    return G, torch.stack([m_[0] for m_ in members]), torch.stack([m_[1] for m_ in members])
+
+
+def _bn_bwd(eng: Engine, g1, g2, act, z, stats, gamma, reducer=None, fused_launch=None, rows=None):
+    """(masked upstream gradient gy, gz = dL/d(conv output), dgamma, dbeta) of one BatchNorm + clip layer over a batch
+    made of G members with their own batch statistics (`stats`: one member's tuple, or a list of them -- the three
+    forwards of a triplet step run as one batch): ds_bn_bwd_group_f32, G = 1 included.  dgamma / dbeta are summed over
+    the members (the reference accumulates them over its three backward passes).  With an active `reducer` the float64
+    sums of ALL members travel in one all-reduce between the reduction and the application (global-batch BatchNorm);
+    dgamma / dbeta then already are the global gradients.  `fused_launch(gy, partial, stream)`: a data-gradient kernel
+    whose epilogue is the reduction (`rows` partial rows per member) runs in place of the reduce step."""
     c = z.shape[-1]
-    Bm = z.shape[0] // G
     dev = z.device
+    G, mean, invstd = _stats_table(stats, c)
     n_pix = (z.numel() // c) // G
-    rows = eng.lib.raw("ds_bn_bwd_partial_rows")(n_pix, c)
-    gy, gz = torch.empty_like(z), torch.empty_like(z)
-    member_sums = torch.empty((2, G, c), dtype=torch.float32, device=dev)      # dgamma / dbeta per member
-    gg_all, gb_all = member_sums[0], member_sums[1]
+    if fused_launch is None:
+        rows = eng.lib.raw("ds_bn_bwd_partial_rows")(n_pix, c)
     st = eng._stream(z)
-
-    def m(t, g):
-        return None if t is None else t[g * Bm:(g + 1) * Bm]
-
-    dp = reducer is not None and reducer.active
+    gy, gz = torch.empty_like(z), torch.empty_like(z)
     partial = torch.empty((G, rows, c, 2), dtype=torch.float32, device=dev)
     coef = torch.empty((G, 3 * c), dtype=torch.float32, device=dev)
-    # the members' statistics as consecutive rows of one table (Engine.forward_train_group lays them out so): all
-    # members' reductions, coefficient sets and applications in four launches instead of 3 G + 2
-    step = c * 4
-    tabled = all(stats[g][0].data_ptr() == stats[0][0].data_ptr() + g * step
-                 and stats[g][1].data_ptr() == stats[0][1].data_ptr() + g * step for g in range(G))
-    if not dp and tabled:
-        gg, gb = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
-        eng.lib.call("ds_bn_bwd_group_f32", eng._p(g1), eng._p(g2), eng._p(act), eng._p(z), eng._p(stats[0][0]),
-                     eng._p(stats[0][1]), eng._p(gamma.detach()), eng._p(gy), eng._p(partial), eng._p(coef),
-                     eng._p(member_sums), eng._p(gg), eng._p(gb), eng._p(gz), n_pix, c, G, st)
-        return gy, gz, gg, gb
-    if dp and tabled:
-        # the same grouped launches, split where the sums of ALL members travel in one all-reduce (2 + 3 launches)
-        sums = torch.empty((G, 2 * c + 1), dtype=torch.float64, device=dev)
-        eng.lib.call("ds_bn_bwd_group_reduce_f32", eng._p(g1), eng._p(g2), eng._p(act), eng._p(z), eng._p(stats[0][0]),
-                     eng._p(stats[0][1]), eng._p(gy), eng._p(partial), eng._p(sums), n_pix, c, G, st)
-        reducer.all_reduce_sum_(sums)
-        gg, gb = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
-        eng.lib.call("ds_bn_bwd_group_apply_f32", eng._p(sums), eng._p(gy), eng._p(z), eng._p(stats[0][0]),
-                     eng._p(stats[0][1]), eng._p(gamma.detach()), eng._p(coef), eng._p(member_sums), eng._p(gg), eng._p(gb),
-                     eng._p(gz), n_pix, c, G, st)
-        return gy, gz, gg, gb
-    if not dp:
-        for g in range(G):
-            mean, invstd = stats[g][0], stats[g][1]
-            eng.lib.call("ds_bn_bwd_f32", eng._p(m(g1, g)), eng._p(m(g2, g)), eng._p(m(act, g)), eng._p(m(z, g)),
-                         eng._p(mean), eng._p(invstd), eng._p(gamma.detach()), eng._p(m(gy, g)), eng._p(partial[g]),
-                         eng._p(coef[g]), eng._p(gg_all[g]), eng._p(gb_all[g]), eng._p(m(gz, g)), n_pix, c, st)
-    else:
-        sums = torch.empty((G, 2 * c + 1), dtype=torch.float64, device=dev)
-        for g in range(G):
-            mean, invstd = stats[g][0], stats[g][1]
-            eng.lib.call("ds_bn_bwd_reduce_f32", eng._p(m(g1, g)), eng._p(m(g2, g)), eng._p(m(act, g)), eng._p(m(z, g)),
-                         eng._p(mean), eng._p(invstd), eng._p(m(gy, g)), eng._p(partial[g]), n_pix, c, st)
-            eng.lib.call("ds_partial_sum_f64", eng._p(partial[g]), rows, eng._p(sums[g]), c, st)
-        sums[:, 2 * c] = float(n_pix)
-        reducer.all_reduce_sum_(sums)                               # every member of this layer in ONE collective
-        for g in range(G):
-            mean, invstd = stats[g][0], stats[g][1]
-            eng.lib.call("ds_bn_bwd_apply_f32", eng._p(sums[g]), 0, eng._p(m(gy, g)), eng._p(m(z, g)), eng._p(mean),
-                         eng._p(invstd), eng._p(gamma.detach()), eng._p(coef[g]), eng._p(gg_all[g]), eng._p(gb_all[g]),
-                         eng._p(m(gz, g)), n_pix, c, st)
+    member_sums = torch.empty((2, G, c), dtype=torch.float32, device=dev)      # dgamma / dbeta per member
     gg, gb = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
-    eng.lib.call("ds_colsum_f32", eng._p(gg_all), eng._p(gg), G, c, st)
-    eng.lib.call("ds_colsum_f32", eng._p(gb_all), eng._p(gb), G, c, st)
-    return gy, gz, gg, gb
-
-
-def _bn_bwd(eng: Engine, g1, g2, act, z, stats, gamma, reducer=None):
-    """(masked upstream gradient gy, gz = dL/d(conv output), dgamma, dbeta).  With a `reducer` the two
-    per-channel sums are all-reduced between the reduce and the apply kernel (global-batch BatchNorm);
-    dgamma / dbeta then already are the global gradients."""
-    if isinstance(stats, list):
-        return _bn_bwd_group(eng, g1, g2, act, z, stats, gamma, reducer)
-    mean, invstd = stats[0], stats[1]
-    c = z.shape[-1]
-    n_pix = z.numel() // c
-    dev = z.device
-    rows = eng.lib.raw("ds_bn_bwd_partial_rows")(n_pix, c)
-    gy = torch.empty_like(z)
-    gz = torch.empty_like(z)
-    partial = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-    coef = torch.empty(3 * c, dtype=torch.float32, device=dev)
-    gg = torch.empty(c, dtype=torch.float32, device=dev)
-    gb = torch.empty_like(gg)
+    tail = (eng._p(z), eng._p(mean), eng._p(invstd), eng._p(gamma.detach()), eng._p(coef), eng._p(member_sums),
+            eng._p(gg), eng._p(gb), eng._p(gz), n_pix, c, G, st)
+    if fused_launch is not None:
+        fused_launch(gy, partial, st)
     if reducer is not None and reducer.active:
-        st = eng._stream(z)
-        eng.lib.call("ds_bn_bwd_reduce_f32", eng._p(g1), eng._p(g2), eng._p(act), eng._p(z), eng._p(mean),
-                     eng._p(invstd), eng._p(gy), eng._p(partial), n_pix, c, st)
-        sums = torch.empty(2 * c + 1, dtype=torch.float64, device=dev)
-        eng.lib.call("ds_partial_sum_f64", eng._p(partial), rows, eng._p(sums), c, st)
-        sums[2 * c] = float(n_pix)
-        reducer.all_reduce_sum_(sums)
-        eng.lib.call("ds_bn_bwd_apply_f32", eng._p(sums), 0, eng._p(gy), eng._p(z),
-                     eng._p(mean), eng._p(invstd), eng._p(gamma.detach()), eng._p(coef), eng._p(gg), eng._p(gb),
-                     eng._p(gz), n_pix, c, st)
-        return gy, gz, gg, gb
-    eng.lib.call("ds_bn_bwd_f32", eng._p(g1), eng._p(g2), eng._p(act), eng._p(z), eng._p(mean), eng._p(invstd),
-                 eng._p(gamma.detach()), eng._p(gy), eng._p(partial), eng._p(coef), eng._p(gg), eng._p(gb),
-                 eng._p(gz), n_pix, c, eng._stream(z))
+        # split where the sums of ALL members travel in one all-reduce (2 + 3 launches)
+        sums = torch.empty((G, 2 * c + 1), dtype=torch.float64, device=dev)
+        if fused_launch is not None:
+            eng.lib.call("ds_partial_sum_f64_group", eng._p(partial), rows, eng._p(sums), n_pix, c, G, st)
+        else:
+            eng.lib.call("ds_bn_bwd_group_reduce_f32", eng._p(g1), eng._p(g2), eng._p(act), eng._p(z), eng._p(mean),
+                         eng._p(invstd), eng._p(gy), eng._p(partial), eng._p(sums), n_pix, c, G, st)
+        reducer.all_reduce_sum_(sums)                               # every member of this layer in ONE collective
+        eng.lib.call("ds_bn_bwd_group_apply_f32", eng._p(sums), eng._p(gy), *tail)
+    elif fused_launch is not None:
+        eng.lib.call("ds_bn_bwd_group_finish_f32", eng._p(partial), rows, eng._p(gy), *tail)
+    else:
+        eng.lib.call("ds_bn_bwd_group_f32", eng._p(g1), eng._p(g2), eng._p(act), eng._p(z), eng._p(mean), eng._p(invstd),
+                     eng._p(gamma.detach()), eng._p(gy), eng._p(partial), eng._p(coef), eng._p(member_sums), eng._p(gg),
+                     eng._p(gb), eng._p(gz), n_pix, c, G, st)
     return gy, gz, gg, gb
 
 
@@ -136,38 +85,10 @@ def _fused_plan(eng: Engine, rows_entry: str, shp: ConvShape, bank_bf16, stats, 
     step = c * 4
     if any(len(m_) < n_tables for m_ in members):
         return None
-    if not all(members[g][k].data_ptr() == members[0][k].data_ptr() + g * step for g in range(G) for k in range(n_tables)):
+    if not all(m_[k].data_ptr() == members[0][k].data_ptr() + g * step for g, m_ in enumerate(members) for k in range(n_tables)):
         return None
     rows = eng.lib.raw(rows_entry)(ctypes.byref(shp), G)
     return (members, rows) if rows > 0 else None
-
-
-def _fused_bn_bwd(eng: Engine, fused_launch, rows: int, G: int, z, mean, invstd, gamma, reducer=None):
-    """What the two fused helpers below share: the buffers, `fused_launch(gy, partial, stream)` -- the data-gradient kernel
-    that writes the masked gradient and the per-tile partial sums --, then the members' sums (through one all-reduce under
-    data parallelism) and the application.  Returns (gy, gz, dgamma, dbeta) like `_bn_bwd`."""
-    c = z.shape[-1]
-    dev = z.device
-    n_pix = (z.numel() // c) // G
-    st = eng._stream(z)
-    gy, gz = torch.empty_like(z), torch.empty_like(z)
-    partial = torch.empty((G, rows, c, 2), dtype=torch.float32, device=dev)
-    coef = torch.empty((G, 3 * c), dtype=torch.float32, device=dev)
-    member_sums = torch.empty((2, G, c), dtype=torch.float32, device=dev)
-    gg, gb = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
-    fused_launch(gy, partial, st)
-    if reducer is not None and reducer.active:
-        sums = torch.empty((G, 2 * c + 1), dtype=torch.float64, device=dev)
-        eng.lib.call("ds_partial_sum_f64_group", eng._p(partial), rows, eng._p(sums), n_pix, c, G, st)
-        reducer.all_reduce_sum_(sums)                               # every member of this layer in ONE collective
-        eng.lib.call("ds_bn_bwd_group_apply_f32", eng._p(sums), eng._p(gy), eng._p(z), eng._p(mean), eng._p(invstd),
-                     eng._p(gamma.detach()), eng._p(coef), eng._p(member_sums), eng._p(gg), eng._p(gb), eng._p(gz),
-                     n_pix, c, G, st)
-    else:
-        eng.lib.call("ds_bn_bwd_group_finish_f32", eng._p(partial), rows, eng._p(gy), eng._p(z), eng._p(mean),
-                     eng._p(invstd), eng._p(gamma.detach()), eng._p(coef), eng._p(member_sums), eng._p(gg), eng._p(gb),
-                     eng._p(gz), n_pix, c, G, st)
-    return gy, gz, gg, gb
 
 
 def _dgrad_bn_bwd(eng: Engine, shp: ConvShape, gz_up, bank_bf16, g2, z, stats, gamma, reducer=None):
@@ -187,7 +108,7 @@ def _dgrad_bn_bwd(eng: Engine, shp: ConvShape, gz_up, bank_bf16, g2, z, stats, g
         eng.lib.call("ds_conv_dgrad_bnbwd_bf16", ctypes.byref(shp), eng._p(gz_up), eng._p(bank_bf16[0]), eng._p(bank_bf16[1]),
                      eng._p(g2), eng._p(z), eng._p(mean), eng._p(invstd), eng._p(sc), eng._p(sh), G, eng._p(gy),
                      eng._p(partial), st)
-    return _fused_bn_bwd(eng, fused_launch, rows, G, z, mean, invstd, gamma, reducer)
+    return _bn_bwd(eng, None, None, None, z, stats, gamma, reducer, fused_launch, rows)
 
 
 def _dgrad_s2_bn_bwd(eng: Engine, shp: ConvShape, gz_up, bank_bf16, act, z, stats, gamma, reducer=None):
@@ -205,7 +126,7 @@ def _dgrad_s2_bn_bwd(eng: Engine, shp: ConvShape, gz_up, bank_bf16, act, z, stat
         eng.lib.call("ds_conv_dgrad_s2_bnbwd_bf16", ctypes.byref(shp), eng._p(gz_up), eng._p(bank_bf16[0]),
                      eng._p(bank_bf16[1]), eng._p(act), eng._p(z), eng._p(mean), eng._p(invstd), G, eng._p(gy),
                      eng._p(partial), st)
-    return _fused_bn_bwd(eng, fused_launch, rows, G, z, mean, invstd, gamma, reducer)
+    return _bn_bwd(eng, None, None, None, z, stats, gamma, reducer, fused_launch, rows)
 
 
 def _wgrad_call(eng: Engine, workspace_entry: str, entry: str, shp: ConvShape, x, gz, out, *tail):

@@ -427,8 +427,8 @@ class Engine:
             shift = torch.empty_like(scale)
         if reducer is not None and reducer.active:
             sums = torch.empty(2 * c + 1, dtype=torch.float64, device=dev)
-            self.lib.call("ds_partial_sum_f64", self._p(stats), stats.shape[0], self._p(sums), c, self._stream(stats))
-            sums[2 * c] = float(count)
+            self.lib.call("ds_partial_sum_f64_group", self._p(stats), stats.shape[0], self._p(sums), count, c, 1,
+                          self._stream(stats))                    # (G = 1: the kernel writes the count slot itself)
             reducer.all_reduce_sum_(sums)
             self._bn_from_sums(sums, bn, (mean, invstd, scale, shift), update_running)
             return mean, invstd, scale, shift
@@ -922,12 +922,11 @@ class Engine:
                                   self._stream(z))
                 else:
                     for g in range(G):
-                        self.lib.call("ds_partial_sum_f64", self._p(sts[g]), sts[g].shape[0], self._p(sums[g]), cout,
-                                      self._stream(z))
-                    sums[:, 2 * cout] = float(count)
+                        self.lib.call("ds_partial_sum_f64_group", self._p(sts[g]), sts[g].shape[0], self._p(sums[g]), count,
+                                      cout, 1, self._stream(z))
                 reducer.all_reduce_sum_(sums)                     # all members of this layer in ONE collective
             # the members' mean / invstd (and scale / shift) as rows of one [G][C] tensor each: the backward pass then
-            # runs every BatchNorm layer's reductions for all members in one launch (backward._bn_bwd_group), or
+            # runs every BatchNorm layer's reductions for all members in one launch (backward._bn_bwd), or
             # inside the data-gradient kernel above it (backward._dgrad_bn_bwd)
             per = list(zip(*torch.empty((4, G, cout), dtype=torch.float32, device=dev)))
             for g in range(G):                                    # running statistics update in call order

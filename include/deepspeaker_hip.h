@@ -369,7 +369,8 @@ int ds_conv_wgrad_bf16(const ds_conv_shape *s, const float *x, const float *gy, 
 /* BatchNorm (train mode) backward in one call: gy = (g1 [+ g2]) masked by the clipped-ReLU of `act`
  * (NULL: unmasked); reductions sum gy, sum gy*xhat; ggamma, gbeta; gz = dL/d(conv output).
  * partial: ds_bn_bwd_partial_rows(n_pix, C) * C * 2 floats; coef: 3*C floats; gy is written (it is the
- * masked gradient the residual branch re-uses). */
+ * masked gradient the residual branch re-uses).  This is the G = 1 case of ds_bn_bwd_group_f32 below (the same kernels,
+ * three launches, no member_sums); the package's own Python calls the grouped form. */
 int ds_bn_bwd_partial_rows(long long n_pix, int C);
 int ds_bn_bwd_f32(const float *g1, const float *g2, const float *act, const float *z,
                   const float *mean, const float *invstd, const float *gamma, float *gy,
@@ -378,7 +379,8 @@ int ds_bn_bwd_f32(const float *g1, const float *g2, const float *act, const floa
 /* the same for a batch made of G members with their own batch statistics (the three forwards of a triplet step run as
  * one batch, train_triplet.py:215), in four launches: tensors [G * n_pix, C]; mean, invstd [G][C]; partial
  * G * ds_bn_bwd_partial_rows(n_pix, C) * C * 2 floats; coef [G][3C]; member_sums [2][G][C] scratch; ggamma / gbeta [C] =
- * the members' gradients added in member order (what three backward passes accumulate into .grad) */
+ * the members' gradients added in member order (what three backward passes accumulate into .grad).  G = 1: three
+ * launches, dgamma / dbeta are written in place and member_sums is not touched. */
 int ds_bn_bwd_group_f32(const float *g1, const float *g2, const float *act, const float *z, const float *mean,
                         const float *invstd, const float *gamma, float *gy, float *partial, float *coef,
                         float *member_sums, float *ggamma, float *gbeta, float *gz, long long n_pix, int C, int G,
@@ -430,7 +432,10 @@ int ds_colsum_f32(const float *x, float *out, int R, int C, void *stream);
 /* ---- split forms for data-parallel training (one process per GPU): the caller all-reduces the
  *      [C][2] float64 sums over RCCL between the two halves, so that N ranks normalise with the
  *      statistics of the GLOBAL batch exactly like one process would.  count == 0:
- *      the (all-reduced) pixel count is read from sums[2*C] on the device -- no host sync. ------- */
+ *      the (all-reduced) pixel count is read from sums[2*C] on the device -- no host sync.
+ *      ds_partial_sum_f64, ds_bn_bwd_reduce_f32 and ds_bn_bwd_apply_f32 are the G = 1 cases of
+ *      ds_partial_sum_f64_group, ds_bn_bwd_group_reduce_f32 (without its fold) and ds_bn_bwd_group_apply_f32
+ *      (with an explicit count); ds_partial_sum_f64 writes [C][2] only, never the count slot. ------- */
 int ds_partial_sum_f64(const float *partial, int n_partial, double *sums, int C, void *stream);
 int ds_bn_stats_from_sums_f32(const double *sums, long long count, const float *gamma,
                               const float *beta, float eps, float momentum, float *running_mean,

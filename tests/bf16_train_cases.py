@@ -8,7 +8,7 @@ test_gpu_bf16_train_kernels.py (MI355X, torch device memory).
        every tile configuration; members, parity classes, refusals)
     c. ds_conv5x5s2_c1_fwd_f32 / _bf16
     d. the f32 BatchNorm family: statistics -> tables -> normalise -> fold; backward in its one-call, split and grouped
-       forms; ds_colsum_f32
+       forms (G = 1 and 3) and the arguments its entry points refuse; ds_colsum_f32
 
 The adapter (`be`):
     be.lib                      the NativeLib
@@ -577,9 +577,17 @@ BN_BWD_ROWS = {(64, 300000): 2048, (512, 40): 3}
 BN_BWD_GROUP_MAX_PIX = 2000                 # the grouped form (G = 3) runs where three members stay small
 
 
+def _same_all(be, got, want, names, what):
+    for name in names:
+        assert be.same(got[name], want[name]), f"{what}: {name}"
+
+
 def body_bn_bwd(be, C, n_pix, with_g2, with_act):
-    """ds_bn_bwd_f32 against float64; the split form (reduce -> float64 fold -> apply) and the grouped form (G = 3, its
-    members' dgamma / dbeta folded by ds_colsum_f32) agree with it bit for bit"""
+    """ds_bn_bwd_f32 against float64; the split form (reduce -> float64 fold -> apply), the grouped entry points with
+    G = 1 (what backward._bn_bwd calls for one member: one call, reduce + apply, finish) and the grouped form (G = 3, its
+    members' dgamma / dbeta folded by ds_colsum_f32; one call, reduce + apply, finish) agree with it bit for bit.  With
+    G = 1 the member_sums scratch is NOT touched (the coefficient kernel writes dgamma / dbeta in place, no member sum);
+    ds_partial_sum_f64 leaves the count slot behind its [C][2] alone, the grouped reduce writes it."""
     lib, p = be.lib, be.p
     G = 3 if n_pix <= BN_BWD_GROUP_MAX_PIX else 1
     rows = lib.raw("ds_bn_bwd_partial_rows")(n_pix, C)
@@ -620,6 +628,36 @@ def body_bn_bwd(be, C, n_pix, with_g2, with_act):
         for a, c, what in ((gy, gy2, "gy"), (gz, gz2, "gz"), (partial, partial2, "partial"), (coef, coef2, "coef"),
                            (gg, gg2, "dgamma"), (gb, gb2, "dbeta")):
             assert be.same(a, c), f"split form: {what} of member {m}"
+        sums_h = be.get(sums)
+        assert np.isfinite(sums_h[:2 * C]).all() and np.isnan(sums_h[2 * C]), "ds_partial_sum_f64 writes [C][2], no count"
+        # the grouped entry points with G = 1
+        want = dict(gy=gy, gz=gz, partial=partial, coef=coef, gg=gg, gb=gb)
+        names = ("gy", "gz", "partial", "coef", "gg", "gb")
+
+        def fresh():
+            o = dict(gy=be.nan((n_pix, C), F32), gz=be.nan((n_pix, C), F32), partial=be.nan((rows, C, 2), F32),
+                     coef=be.nan(3 * C, F32), gg=be.nan(C, F32), gb=be.nan(C, F32), msums=be.nan((2, 1, C), F32))
+            tail = (p(member(z_d, m)), p(mu), p(is_), p(gm), p(o["coef"]), p(o["msums"]), p(o["gg"]), p(o["gb"]), p(o["gz"]),
+                    n_pix, C, 1, be.stream)
+            return o, tail
+
+        o, _ = fresh()
+        lib.call("ds_bn_bwd_group_f32", *args, p(gm), p(o["gy"]), p(o["partial"]), p(o["coef"]), p(o["msums"]), p(o["gg"]),
+                 p(o["gb"]), p(o["gz"]), n_pix, C, 1, be.stream)
+        _same_all(be, o, want, names, f"ds_bn_bwd_group_f32, G = 1, member {m}")
+        assert np.isnan(be.get(o["msums"])).all(), "G = 1: member_sums is not touched"
+        o, tail = fresh()
+        sums1 = be.nan((1, 2 * C + 1), F64)
+        lib.call("ds_bn_bwd_group_reduce_f32", *args, p(o["gy"]), p(o["partial"]), p(sums1), n_pix, C, 1, be.stream)
+        assert be.get(sums1)[0, 2 * C] == n_pix
+        assert np.array_equal(be.get(sums1)[0, :2 * C], sums_h[:2 * C])
+        lib.call("ds_bn_bwd_group_apply_f32", p(sums1), p(o["gy"]), *tail)
+        _same_all(be, o, want, names, f"group reduce + apply, G = 1, member {m}")
+        assert np.isnan(be.get(o["msums"])).all(), "G = 1: member_sums is not touched"
+        o, tail = fresh()
+        lib.call("ds_bn_bwd_group_finish_f32", p(partial), rows, p(gy), *tail)
+        _same_all(be, o, want, ("gz", "coef", "gg", "gb"), f"ds_bn_bwd_group_finish_f32, G = 1, member {m}")
+        assert np.isnan(be.get(o["msums"])).all(), "G = 1: member_sums is not touched"
         gz_ref, gg_ref, gb_ref = O.bn_train_bwd(zs[m].T.reshape(1, C, n_pix, 1), mean[m].astype(F64), invstd[m].astype(F64),
                                                 gamma.astype(F64), gy_ref[m].T.reshape(1, C, n_pix, 1))
         assert np.isfinite(be.get(partial)).all()
@@ -647,6 +685,109 @@ def body_bn_bwd(be, C, n_pix, with_g2, with_act):
         folded = be.nan(C, F32)
         lib.call("ds_colsum_f32", p(stacked), p(folded), G, C, be.stream)
         assert be.same(got, folded), what
+    # the grouped form split at the all-reduce, and its second half alone from the grouped partial rows
+    want = dict(gy=gy, gz=gz, partial=partial, coef=coef, msums=msums, gg=gg, gb=gb)
+
+    def fresh():
+        o = dict(gy=be.nan((G * n_pix, C), F32), gz=be.nan((G * n_pix, C), F32), partial=be.nan((G, rows, C, 2), F32),
+                 coef=be.nan((G, 3 * C), F32), msums=be.nan((2, G, C), F32), gg=be.nan(C, F32), gb=be.nan(C, F32))
+        tail = (p(z_d), p(mean_d), p(invstd_d), p(gm), p(o["coef"]), p(o["msums"]), p(o["gg"]), p(o["gb"]), p(o["gz"]),
+                n_pix, C, G, be.stream)
+        return o, tail
+
+    o, tail = fresh()
+    sums = be.nan((G, 2 * C + 1), F64)
+    lib.call("ds_bn_bwd_group_reduce_f32", p(g1_d), p(g2_d), p(act_d), p(z_d), p(mean_d), p(invstd_d), p(o["gy"]),
+             p(o["partial"]), p(sums), n_pix, C, G, be.stream)
+    assert (be.get(sums)[:, 2 * C] == n_pix).all()
+    lib.call("ds_bn_bwd_group_apply_f32", p(sums), p(o["gy"]), *tail)
+    _same_all(be, o, want, ("gy", "gz", "partial", "coef", "msums", "gg", "gb"), "group reduce + apply, G = 3")
+    o, tail = fresh()
+    lib.call("ds_bn_bwd_group_finish_f32", p(partial), rows, p(gy), *tail)
+    _same_all(be, o, want, ("gz", "coef", "msums", "gg", "gb"), "ds_bn_bwd_group_finish_f32, G = 3")
+
+
+# The argument lists of the f32 BatchNorm backward's entry points and the calls they REFUSE: (entry point, argument, bad
+# value, return code) with None = a null pointer and "+4" = the pointer moved by 4 bytes; everything else about the call is
+# valid (n_pix 16, C 8, G 2, one partial row).  The codes are those of the library before the entry points shared their
+# launches (-1 bad shape, -2 alignment, -3 null): each entry point checks what it always checked, and they differ -- only the
+# grouped forms look at the alignment of g2, ds_bn_bwd_apply_f32 and the float64 folds at none, and the folds take any C > 0.
+# Only refused calls are listed: one that is accepted would launch with the bad argument.
+BN_BWD_ARGS = {
+    "ds_bn_bwd_f32": "g1 g2 act z mean invstd gamma gy partial coef gg gb gz n_pix C",
+    "ds_bn_bwd_reduce_f32": "g1 g2 act z mean invstd gy partial n_pix C",
+    "ds_bn_bwd_apply_f32": "sums count gy z mean invstd gamma coef gg gb gz n_pix C",
+    "ds_bn_bwd_group_f32": "g1 g2 act z mean invstd gamma gy partial coef msums gg gb gz n_pix C G",
+    "ds_bn_bwd_group_reduce_f32": "g1 g2 act z mean invstd gy partial sums n_pix C G",
+    "ds_bn_bwd_group_apply_f32": "sums gy z mean invstd gamma coef msums gg gb gz n_pix C G",
+    "ds_bn_bwd_group_finish_f32": "partial n_partial gy z mean invstd gamma coef msums gg gb gz n_pix C G",
+    "ds_partial_sum_f64": "partial n_partial sums C",
+    "ds_partial_sum_f64_group": "partial n_partial sums count C G",
+}
+BN_BWD_REFUSALS = [
+    ("ds_bn_bwd_f32", "z", None, -3), ("ds_bn_bwd_f32", "gb", None, -3), ("ds_bn_bwd_f32", "C", 6, -1),
+    ("ds_bn_bwd_f32", "C", 2048, -1), ("ds_bn_bwd_f32", "n_pix", 0, -1), ("ds_bn_bwd_f32", "g1", "+4", -2),
+    ("ds_bn_bwd_f32", "coef", "+4", -2),
+    ("ds_bn_bwd_reduce_f32", "partial", None, -3), ("ds_bn_bwd_reduce_f32", "C", 6, -1),
+    ("ds_bn_bwd_reduce_f32", "n_pix", 0, -1), ("ds_bn_bwd_reduce_f32", "g1", "+4", -2),
+    ("ds_bn_bwd_apply_f32", "sums", None, -3), ("ds_bn_bwd_apply_f32", "gamma", None, -3),
+    ("ds_bn_bwd_apply_f32", "C", 6, -1), ("ds_bn_bwd_apply_f32", "n_pix", 0, -1), ("ds_bn_bwd_apply_f32", "count", -1, -1),
+    ("ds_bn_bwd_group_f32", "z", None, -3), ("ds_bn_bwd_group_f32", "msums", None, -3), ("ds_bn_bwd_group_f32", "C", 6, -1),
+    ("ds_bn_bwd_group_f32", "G", 0, -1), ("ds_bn_bwd_group_f32", "G", 65, -1), ("ds_bn_bwd_group_f32", "n_pix", 0, -1),
+    ("ds_bn_bwd_group_f32", "g1", "+4", -2), ("ds_bn_bwd_group_f32", "g2", "+4", -2), ("ds_bn_bwd_group_f32", "act", "+4", -2),
+    ("ds_bn_bwd_group_reduce_f32", "sums", None, -3), ("ds_bn_bwd_group_reduce_f32", "C", 6, -1),
+    ("ds_bn_bwd_group_reduce_f32", "G", 0, -1), ("ds_bn_bwd_group_reduce_f32", "G", 65, -1),
+    ("ds_bn_bwd_group_reduce_f32", "n_pix", 0, -1), ("ds_bn_bwd_group_reduce_f32", "g1", "+4", -2),
+    ("ds_bn_bwd_group_reduce_f32", "g2", "+4", -2),
+    ("ds_bn_bwd_group_apply_f32", "sums", None, -3), ("ds_bn_bwd_group_apply_f32", "msums", None, -3),
+    ("ds_bn_bwd_group_apply_f32", "C", 6, -1), ("ds_bn_bwd_group_apply_f32", "G", 0, -1),
+    ("ds_bn_bwd_group_apply_f32", "G", 65, -1), ("ds_bn_bwd_group_apply_f32", "n_pix", 0, -1),
+    ("ds_bn_bwd_group_apply_f32", "gy", "+4", -2),
+    ("ds_bn_bwd_group_finish_f32", "partial", None, -3), ("ds_bn_bwd_group_finish_f32", "C", 6, -1),
+    ("ds_bn_bwd_group_finish_f32", "G", 0, -1), ("ds_bn_bwd_group_finish_f32", "G", 65, -1),
+    ("ds_bn_bwd_group_finish_f32", "n_pix", 0, -1), ("ds_bn_bwd_group_finish_f32", "n_partial", 0, -1),
+    ("ds_bn_bwd_group_finish_f32", "coef", "+4", -2),
+    ("ds_partial_sum_f64", "sums", None, -3), ("ds_partial_sum_f64", "C", 0, -1), ("ds_partial_sum_f64", "n_partial", 0, -1),
+    ("ds_partial_sum_f64_group", "partial", None, -3), ("ds_partial_sum_f64_group", "C", 0, -1),
+    ("ds_partial_sum_f64_group", "G", 0, -1), ("ds_partial_sum_f64_group", "G", 65, -1),
+    ("ds_partial_sum_f64_group", "n_partial", 0, -1), ("ds_partial_sum_f64_group", "count", 0, -1),
+]
+
+
+def bn_bwd_refused_calls(be, refusals):
+    """[(entry point, argument, bad value, return code of the call)] for `refusals`, then: nothing was written"""
+    n_pix, C, G = 16, 8, 2
+    shapes = dict(g1=(G * n_pix, C), g2=(G * n_pix, C), act=(G * n_pix, C), z=(G * n_pix, C), gy=(G * n_pix, C),
+                  gz=(G * n_pix, C), mean=(G, C), invstd=(G, C), gamma=(C,), partial=(G, 1, C, 2), coef=(G, 3 * C),
+                  msums=(2, G, C), gg=(C,), gb=(C,))
+    bufs = {name: be.nan(shape, F32) for name, shape in shapes.items()}
+    bufs["sums"] = be.nan((G, 2 * C + 1), F64)
+    scalars = dict(n_pix=n_pix, C=C, G=G, n_partial=1, count=n_pix)
+    assert be.lib.raw("ds_bn_bwd_partial_rows")(n_pix, C) == 1
+    got = []
+    for entry, arg, bad, _ in refusals:
+        names = BN_BWD_ARGS[entry].split()
+        assert arg in names, (entry, arg)
+        args = []
+        for name in names:
+            v = scalars[name] if name in scalars else address(be.p(bufs[name]))
+            if name == arg:
+                v = v + 4 if bad == "+4" else bad
+            args.append(v)
+        got.append((entry, arg, bad, be.lib.raw(entry)(*args, be.stream)))
+    for name, h in bufs.items():
+        assert np.isnan(be.get(h)).all(), f"a refused call wrote to {name}"
+    return got
+
+
+def body_bn_bwd_refusals(be):
+    """every entry point of the f32 BatchNorm backward refuses what it refused before, with the same code, and launches
+    nothing"""
+    got = bn_bwd_refused_calls(be, BN_BWD_REFUSALS)
+    for row in got:
+        print("refused: %s(%s = %r) -> %d" % row)
+    assert all(rc != 0 for _, _, _, rc in got)
+    assert got == BN_BWD_REFUSALS
 
 
 COLSUM_CASES = [(1031, 77), (3, 512), (40, 32)]                     # (rows, columns): columns no multiple of the 32 per workgroup

@@ -96,6 +96,10 @@ def test_bn_bwd(be, C, n_pix, with_g2, with_act):
     BC.body_bn_bwd(be, C, n_pix, with_g2, with_act)
 
 
+def test_bn_bwd_refusals(be):
+    BC.body_bn_bwd_refusals(be)
+
+
 @pytest.mark.parametrize("R,C", BC.COLSUM_CASES)
 def test_colsum(be, R, C):
     BC.body_colsum(be, R, C)

@@ -10,7 +10,8 @@ test_emul_bf16_train.py.
     c. ds_conv5x5s2_c1_fwd_f32 / _bf16
     d. ds_bn_stats_finalize_f32 (on the rows of a real ds_conv_fwd_f32 launch), ds_partial_sum_f64 +
        ds_bn_stats_from_sums_f32, ds_bn_apply_f32, ds_bn_fold_f32; ds_bn_bwd_f32 up to the 2048-row cap, its split form
-       (ds_bn_bwd_reduce_f32 / ds_bn_bwd_apply_f32) and ds_bn_bwd_group_f32 + ds_colsum_f32 bit for bit
+       (ds_bn_bwd_reduce_f32 / ds_bn_bwd_apply_f32) and ds_bn_bwd_group_f32 + ds_colsum_f32 bit for bit; the grouped entry
+       points with G = 1 and the split / finish forms with G = 3 bit for bit; the calls the nine entry points refuse
 
 Bars (the emulator suite's own; max-norm relative errors).  Forward: bf16x3 2e-5, plain bf16 in (1e-4, 2e-2); statistics
 rtol 1e-4 beyond atol 1e-3 (plain: 2e-2 beyond 0.5).  Fused data gradient: gy 3e-5; gz, dgamma, dbeta 1e-4; the partial
@@ -124,6 +125,10 @@ def test_bn_forward_chain(be, case):
 @pytest.mark.parametrize("C,n_pix,with_g2,with_act", BC.BN_BWD_CASES)
 def test_bn_bwd(be, C, n_pix, with_g2, with_act):
     BC.body_bn_bwd(be, C, n_pix, with_g2, with_act)
+
+
+def test_bn_bwd_refusals(be):
+    BC.body_bn_bwd_refusals(be)
 
 
 @pytest.mark.parametrize("R,C", BC.COLSUM_CASES)

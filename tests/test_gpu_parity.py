@@ -456,11 +456,17 @@ def test_data_parallel_world1_nccl(dev, precision, streams):
                 if grouped:     # the grouped launch sequence, split at the all-reduce -- no per-member fallback
                     assert trace.get("ds_bn_bwd_group_reduce_f32", 0) + fused == 12 and trace.get("ds_bn_bwd_group_apply_f32") == 12
                     assert "ds_bn_bwd_reduce_f32" not in trace
-                    # forward: one fold per layer for all members (lock-step) or one per layer and member (streams)
-                    assert (trace.get("ds_partial_sum_f64_group", 0) + trace.get("ds_partial_sum_f64", 0) // 3
-                            == (36 if streams else 12) + fused)
+                    # forward: one fold per layer for all members (lock-step) or one per layer and member (streams); in
+                    # lock-step a layer whose tiles would straddle members runs one convolution and one fold (G = 1) per
+                    # member: 11 stage convolutions + 2 more per such layer
+                    convs = trace.get("ds_conv_fwd_bf16" if precision == "bf16x3" else "ds_conv_fwd_f32", 0)
+                    assert convs >= 11 and (convs - 11) % 2 == 0, convs
+                    assert "ds_partial_sum_f64" not in trace
+                    assert trace.get("ds_partial_sum_f64_group", 0) == (36 if streams else 12 + (convs - 11)) + fused
                 else:
-                    assert trace.get("ds_bn_bwd_reduce_f32", 0) + fused == 36 and trace.get("ds_bn_stats_from_sums_f32") == 36
+                    # one member per call: the grouped entry points with G = 1
+                    assert trace.get("ds_bn_bwd_group_reduce_f32", 0) + fused == 36
+                    assert trace.get("ds_bn_bwd_group_apply_f32") == 36 and trace.get("ds_bn_stats_from_sums_f32") == 36
             Engine.MEMBER_STREAMS = True
             grads.append({n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None})
             losses.append(float(loss))

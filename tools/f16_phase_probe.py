@@ -21,7 +21,7 @@ OUT = "/tmp/libds_probe.so"
 srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DDS_F16_PROBE",
                 "-mllvm", "-pragma-unroll-threshold=1000000", "-Wno-pass-failed", f"-I{CSRC}", f"-I{ROOT}/include",
-                *sys.argv[1:], "-o", OUT, *[s for s in srcs if "f16" in s or "bn_pack" in s or "tail_loss" in s]],
+                *sys.argv[1:], "-o", OUT, *[s for s in srcs if "f16" in s or "bn_pack" in s or "runtime" in s or "tail_loss" in s]],
                check=True)
 dll = ctypes.CDLL(OUT)
 dev = torch.device("cuda", 0)

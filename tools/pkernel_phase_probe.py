@@ -20,7 +20,7 @@ OUT = os.path.join(ROOT, "tools", "_ab", "libds_pkprobe.so")
 if "--build-only" in sys.argv:
     objd = os.path.join(ROOT, "tools", "_ab", "obj_pkprobe")
     os.makedirs(objd, exist_ok=True)
-    srcs = [s for s in sorted(glob.glob(os.path.join(CSRC, "*.hip"))) if "conv_mfma_f16" in s or "bn_pack" in s]
+    srcs = [s for s in sorted(glob.glob(os.path.join(CSRC, "*.hip"))) if "conv_mfma_f16" in s or "runtime" in s]
 
     def cc(s):
         o = os.path.join(objd, os.path.basename(s)[:-4] + ".o")
