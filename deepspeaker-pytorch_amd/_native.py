@@ -18,6 +18,7 @@ DS_CONV_HINT_CHUNK16 = 128
 DS_CONV_HINT_NO_PERSIST = 1024
 DS_CONV_HINT_NO_WIDE = 2048
 DS_CONV_HINT_ONE_QUEUE = 4096
+DS_CONV_PLAN_LATENCY = 8192
 DS_CONV_CK = 8
 DS_TAIL_SMALL_MAX_B = 4
 
@@ -76,6 +77,7 @@ _SIGNATURES = {
     "ds_conv_dgrad_bf16": (c_int, [POINTER(ConvShape), _P, _P, _P, _P, _P]),
     "ds_conv_bf16_stats_rows": (c_int, [POINTER(ConvShape), c_int]),
     "ds_conv_bf16_plan_describe": (c_int, [POINTER(ConvShape), c_int, POINTER(c_int)]),
+    "ds_conv_bf16_plan_describe_hinted": (c_int, [POINTER(ConvShape), c_int, c_int, POINTER(c_int)]),
     "ds_conv_bf16_set_forced_cfg": (None, [c_int]),
     "ds_conv_fwd_bf16": (c_int, [POINTER(ConvShape), _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
     "ds_pack_conv_weight_f16": (c_int, [_P, _P, c_int, c_int, c_int, _P]),

@@ -100,6 +100,10 @@ static double frag_read_cost(int MT, int NI, int RT, int Wc, int IS, int rows_in
 // ---- host-side plan: the shared tile search (conv_plan.h) over the rows of kCfgB (conv_mfma_bf16_kernel.h) ----
 static int g_forced_cfg_b = -1;      // tuning hook (tools/bf16_cfg_ab.py): plan with this tile configuration only
 
+// what a caller of plan_bf16 lets it choose from beyond the rows of kCfgB
+constexpr int kPlanLatRows = 1;      // the caller can launch a latency row (kCfgBLat): the forced-configuration hook may name one
+constexpr int kPlanLatency = 2;      // DS_CONV_PLAN_LATENCY: plan a launch that leaves the chip short of waves for its latency
+
 // LDS of a launch whose pixel tile holds tile_pix records: the tile (hi + lo planes for bf16x3), which the epilogue's
 // buffers alias, then the out_off [MT], seg_lo / seg_cnt [NI] and statistics [WM][NTILE][2] tables.  The launch asks
 // for kLdsSlackB bytes more than this; the configurations' caps are compared against this figure.
@@ -111,8 +115,20 @@ static size_t plan_lds_bytes(const TileCfgB &cf, size_t tile_pix, bool x3, int N
 // `s` describes the tile grid: input [B,H,W,Cin], KS x KS taps, stride s->stride, output grid Ho x Wo computed
 // with `pad`.  The forward convolution writes that grid densely; the stride-2 data gradient runs four such
 // grids (parity classes) whose outputs interleave in y (out_* arguments).
+//
+// mode & kPlanLatency (bf16x3 forward launches only): the search above is run first, and its plan stands wherever it puts
+// at least one wave on every SIMD of the chip -- such a launch is bound by throughput, which is what that search and
+// its tie-breaks were tuned for (so the plans of a 768-utterance batch are the same with and without the flag).  A
+// smaller launch takes as long as one wave's walk over the contraction, so the rows of kCfgB AND kCfgBLat are searched
+// again for the least
+//     (rounds the launch needs: its waves over the chip's SIMDs, rounded up) x (MFMAs of a wave per k-step)
+// -- waves that share a SIMD share its matrix pipe, so a round is one wave per SIMD.  Ties go to the larger tile, then
+// to the fewer workgroups (fuller tiles: less filter traffic and fewer CUs taken from whatever runs next to the launch
+// for the same latency), then to the first search's objective.  Every row
+// accumulates an output element over the same k-steps in the same order (hi*lo, lo*hi, hi*hi per step), so the choice
+// of row never changes a bit of the result.
 static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride = 1, int out_h0 = 0, int out_w0 = 0,
-                     int out_H = 0, int out_W = 0, int grid_H = 0, int grid_W = 0) {
+                     int out_H = 0, int out_W = 0, int grid_H = 0, int grid_W = 0, int mode = 0) {
     int Ho, Wo;
     const int rc = ds_plan_check_shape(s, CKB, false, Ho, Wo, grid_H, grid_W);
     if (rc != DS_OK) return rc;
@@ -123,11 +139,13 @@ static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride 
     const int IS = s->stride;
     double best = -1.0;
     int bc = -1, brt = 0, bni = 0;
-    for (int c = 0; c < kNumCfgB; ++c) {
-        const TileCfgB &cf = kCfgB[c];
-        if (s->Cout % cf.NTILE()) continue;
-        if (cf.x3_only && !x3) continue;
-        if (g_forced_cfg_b >= 0 && c != g_forced_cfg_b) continue;
+    long long bwaves = 0, bcost = 0, bblocks = 0;
+    bool latency = false;           // the second search
+    auto search = [&](int c) {
+        const TileCfgB &cf = ds_bf16_cfg(c);
+        if (s->Cout % cf.NTILE()) return;
+        if (cf.x3_only && !x3) return;
+        if (g_forced_cfg_b >= 0 && c != g_forced_cfg_b) return;
         const long long item_cap = (long long)cf.items_per_thread * cf.NTHR();
         // feasibility with the widest row pitch the conflict search may pick (cols_in + 4); the pitch itself is chosen
         // once, for the winning geometry (this function runs on every launch).  Staged items: 4-channel quarters of
@@ -145,16 +163,33 @@ static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride 
             if (waves < kPlanSIMDs) eff *= (double)waves / (double)kPlanSIMDs;
             // ties: 160x64 register tiles first; for 64 output channels the four-wave 256x64 tile beats the two-wave
             // 320x64 one (same tool: 484 against 525 us at 768 utterances, 173 against 185 at 256)
-            int pref[kNumCfgB] = {0, 2, 7, 8, 5, 6, 1, 4, 3};
+            int pref[kNumCfgBAll] = {0, 2, 7, 8, 5, 6, 1, 4, 3, 0, 0};
 #ifdef DS_BF16_PREF_TOP
             pref[DS_BF16_PREF_TOP] = 9;                               // A/B builds (tools/conv_bf16_ab.py): another tie-break
 #endif
             eff += 1e-9 * rt + 1e-6 * pref[c];
-            if (eff > best) { best = eff; bc = c; brt = rt; bni = ni; }
+            bool better = eff > best;
+            const long long cost = ds_ceil_div_ll(waves, kPlanSIMDs) * ((x3 ? 3 : 1) * cf.MSUB * cf.NSUB);
+            if (latency && bc >= 0) {
+                const TileCfgB &bf = ds_bf16_cfg(bc);
+                const int area = cf.MT() * cf.NTILE(), barea = bf.MT() * bf.NTILE();
+                if (cost != bcost) better = cost < bcost;
+                else if (area != barea) better = area > barea;
+                else if (blocks != bblocks) better = blocks < bblocks;
+            }
+            if (better) { best = eff; bc = c; brt = rt; bni = ni; bwaves = waves; bcost = cost; bblocks = blocks; }
         });
+    };
+    const bool forced_lat = (mode & kPlanLatRows) && g_forced_cfg_b >= kNumCfgB;
+    for (int c = 0; c < (forced_lat ? kNumCfgBAll : kNumCfgB); ++c) search(c);
+    if ((mode & kPlanLatency) && x3 && g_forced_cfg_b < 0 && bc >= 0 && bwaves < kPlanSIMDs) {
+        latency = true;
+        best = -1.0;
+        bc = -1;
+        for (int c = 0; c < kNumCfgBAll; ++c) search(c);
     }
     if (bc < 0) return DS_ERR_UNSUPPORTED;
-    const TileCfgB &cf = kCfgB[bc];
+    const TileCfgB &cf = ds_bf16_cfg(bc);
     ConvKB &k = pl.k;
     k.H = s->H; k.W = s->W; k.Cin = s->Cin;
     k.Hr = Ho; k.Wc = Wo; k.Ho = yH; k.Wo = yW; k.Cout = s->Cout;
@@ -192,6 +227,10 @@ static void set_operands(ConvKB &k, const float *x, const void *w_hi, const void
 // kernel size x arithmetic -> the translation unit that holds those instantiations
 template <int KS, bool X3>
 static void launch_b(const PlanB &pl, void *stream) {
+    if (pl.cfg >= kNumCfgB) {           // a latency row: bf16x3 only (plan_bf16 offers them to no other arithmetic)
+        if (KS == 3) ds_bf16_launch_k3x3l(pl, stream); else ds_bf16_launch_k5x3l(pl, stream);
+        return;
+    }
     if (KS == 3) { if (X3) ds_bf16_launch_k3x3(pl, stream); else ds_bf16_launch_k3x1(pl, stream); }
     else         { if (X3) ds_bf16_launch_k5x3(pl, stream); else ds_bf16_launch_k5x1(pl, stream); }
 }
@@ -252,21 +291,29 @@ extern "C" int ds_pack_conv_weight_dgrad_bf16(const float *w_oihw, void *w_hi, v
     return pack_bf16(w_oihw, w_hi, w_lo, Cout, Cin, KS, 1, stream);
 }
 
+// the plan mode of a forward launch with these `flags`
+static int fwd_plan_mode(int flags) { return kPlanLatRows | ((flags & DS_CONV_PLAN_LATENCY) ? kPlanLatency : 0); }
+
 extern "C" int ds_conv_bf16_stats_rows(const ds_conv_shape *s, int x3) {
     PlanB pl;
-    int rc = plan_bf16(pl, s, x3 != 0);
+    int rc = plan_bf16(pl, s, x3 != 0, 1, 0, 0, 0, 0, 0, 0, fwd_plan_mode(0));
     return rc == DS_OK ? pl.n_mtiles : rc;
 }
 
-// tuning hook: cfg in [0, 9) = plan every bf16 convolution with that tile configuration; anything else = the planner's choice
-extern "C" void ds_conv_bf16_set_forced_cfg(int cfg) { g_forced_cfg_b = (cfg >= 0 && cfg < kNumCfgB) ? cfg : -1; }
+// tuning hook: cfg in [0, 9) = plan every bf16 convolution with that tile configuration, 9 and 10 = the latency rows
+// (bf16x3 forward launches only: every other launch is then refused); anything else = the planner's choice
+extern "C" void ds_conv_bf16_set_forced_cfg(int cfg) { g_forced_cfg_b = (cfg >= 0 && cfg < kNumCfgBAll) ? cfg : -1; }
 
 extern "C" int ds_conv_bf16_plan_describe(const ds_conv_shape *s, int x3, int *out8) {
+    return ds_conv_bf16_plan_describe_hinted(s, x3, 0, out8);
+}
+
+extern "C" int ds_conv_bf16_plan_describe_hinted(const ds_conv_shape *s, int x3, int flags, int *out8) {
     DS_REQUIRE(out8 != nullptr, DS_ERR_NULL);
     PlanB pl;
-    int rc = plan_bf16(pl, s, x3 != 0);
+    int rc = plan_bf16(pl, s, x3 != 0, 1, 0, 0, 0, 0, 0, 0, fwd_plan_mode(flags));
     if (rc != DS_OK) return rc;
-    const TileCfgB &cf = kCfgB[pl.cfg];
+    const TileCfgB &cf = ds_bf16_cfg(pl.cfg);
     out8[0] = cf.MT(); out8[1] = cf.NTILE(); out8[2] = pl.k.RT; out8[3] = pl.k.NI;
     out8[4] = pl.grid; out8[5] = (int)pl.lds_bytes; out8[6] = cf.NTHR(); out8[7] = pl.k.pitch;
     return DS_OK;
@@ -279,12 +326,14 @@ extern "C" int ds_conv_fwd_bf16(const ds_conv_shape *s, const float *x, const vo
     DS_REQUIRE(!(flags & DS_EPI_AFFINE) || (scale && shift), DS_ERR_NULL);
     DS_REQUIRE(!(flags & DS_EPI_RESIDUAL) || residual, DS_ERR_NULL);
     DS_REQUIRE(!(flags & DS_EPI_STATS) || stats_partial, DS_ERR_NULL);
+    // the statistics rows are sized by ds_conv_bf16_stats_rows, i.e. by the plan without the flag
+    DS_REQUIRE(!((flags & DS_CONV_PLAN_LATENCY) && (flags & DS_EPI_STATS)), DS_ERR_UNSUPPORTED);
     DS_REQUIRE(DS_ALIGNED16(x) && DS_ALIGNED16(w_hi) && DS_ALIGNED16(y) && DS_ALIGNED16(w_lo), DS_ERR_ALIGNMENT);
     const bool x3 = w_lo != nullptr;
     PlanB pl;
-    int rc = plan_bf16(pl, s, x3);
+    int rc = plan_bf16(pl, s, x3, 1, 0, 0, 0, 0, 0, 0, fwd_plan_mode(flags));
     if (rc != DS_OK) return rc;
-    set_operands(pl.k, x, w_hi, w_lo, y, scale, shift, residual, stats_partial, flags);
+    set_operands(pl.k, x, w_hi, w_lo, y, scale, shift, residual, stats_partial, flags & ~DS_CONV_PLAN_LATENCY);
     if (s->KS == 3) { if (x3) launch_b<3, true>(pl, stream); else launch_b<3, false>(pl, stream); }
     else            { if (x3) launch_b<5, true>(pl, stream); else launch_b<5, false>(pl, stream); }
     return ds_last_launch_error();

@@ -1,0 +1,6 @@
+// conv_mfma_bf16_k5x3l.hip -- instantiations of conv_mfma_bf16_kernel for 5x5 taps, split-operand bf16x3
+// arithmetic, the latency rows kCfgBLat (one translation unit per combination so that they compile in parallel).
+#define DS_BF16_KERNEL_TU
+#include "conv_mfma_bf16_kernel.h"
+
+void ds_bf16_launch_k5x3l(const PlanB &pl, void *stream) { launch_lat_b<5>(pl, stream); }

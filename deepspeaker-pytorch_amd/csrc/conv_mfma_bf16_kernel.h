@@ -78,12 +78,27 @@ constexpr TileCfgB kCfgB[kNumCfgB] = {
     {4, 2, 1, 4, 1, 160 * 1024 - 64, 32, true},     // 128 x 256: the same with the whole LDS (three 10x4 maps of the last 5x5 layer)
 };
 
+// The latency rows: a register tile of ONE 32 x 32 sub-tile per wave, so a wave issues 3 MFMAs per k-step of a bf16x3
+// product where the smallest row above issues 6 -- for launches so small that the chip is nowhere near full and the
+// time of the launch is one wave's walk over the contraction.  A table of their own: the planner only looks at them
+// under DS_CONV_PLAN_LATENCY (or when one is forced), and `cfg` = kNumCfgB + row.  bf16x3 only; the kernels are the
+// launch_nit_b instantiations (256 threads, default LDS), in translation units of their own.
+constexpr int kNumCfgBLat = 2;
+constexpr TileCfgB kCfgBLat[kNumCfgBLat] = {
+    {1, 1, 2, 2, 2, 64 * 1024, 16, true},           // 64 x 64 (the 3x3 instances hold ~210 registers: two waves per SIMD)
+    {1, 1, 1, 4, 2, 64 * 1024, 16, true},           // 32 x 128
+};
+constexpr int kNumCfgBAll = kNumCfgB + kNumCfgBLat;
+constexpr const TileCfgB &ds_bf16_cfg(int cfg) { return cfg < kNumCfgB ? kCfgB[cfg] : kCfgBLat[cfg - kNumCfgB]; }
+
 // one entry point per translation unit (kernel size x arithmetic)
 void ds_bf16_launch_k3x3(const PlanB &pl, void *stream);
 void ds_bf16_launch_k5x3(const PlanB &pl, void *stream);
 void ds_bf16_launch_k3x1(const PlanB &pl, void *stream);
 void ds_bf16_launch_k5x1(const PlanB &pl, void *stream);
 void ds_bf16_launch_k3x3g(const PlanB &pl, void *stream);      // 3x3 bf16x3 with the BatchNorm-backward epilogue
+void ds_bf16_launch_k3x3l(const PlanB &pl, void *stream);      // the latency rows (pl.cfg >= kNumCfgB), bf16x3
+void ds_bf16_launch_k5x3l(const PlanB &pl, void *stream);
 
 #ifdef DS_BF16_KERNEL_TU
 namespace {
@@ -613,6 +628,17 @@ static void launch_b(const PlanB &pl, void *stream) {
         if constexpr (!cf.x3_only) launch_nit_b<KS, cf.MSUB, cf.NSUB, cf.WM, cf.WN, X3, BNB>(pl, stream);
         else if constexpr (X3) launch_big_b<KS, cf.MSUB, cf.NSUB, cf.WM, cf.WN, BNB>(pl, stream);
     });
+}
+
+// the same for the latency rows: pl.cfg - kNumCfgB -> row of kCfgBLat
+template <int KS, int N = 0>
+static void launch_lat_b(const PlanB &pl, void *stream) {
+    if constexpr (N < kNumCfgBLat) {
+        constexpr TileCfgB cf = kCfgBLat[N];
+        static_assert(cf.NTHR() == 256, "launch_nit_b launches 256 threads");
+        if (pl.cfg - kNumCfgB == N) launch_nit_b<KS, cf.MSUB, cf.NSUB, cf.WM, cf.WN, true>(pl, stream);
+        else launch_lat_b<KS, N + 1>(pl, stream);
+    }
 }
 
 }  // namespace

@@ -16,8 +16,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from ._native import (ConvShape, DS_CONV_IN_PLANES16, DS_EPI_AFFINE, DS_EPI_CLIP, DS_EPI_OUT_F16, DS_EPI_OUT_F32,
-                      DS_EPI_OUT_PLANES16, DS_EPI_RESIDUAL, DS_EPI_STATS, DS_TAIL_SMALL_MAX_B, NativeLib, PackJob)
+from ._native import (ConvShape, DS_CONV_IN_PLANES16, DS_CONV_PLAN_LATENCY, DS_EPI_AFFINE, DS_EPI_CLIP, DS_EPI_OUT_F16,
+                      DS_EPI_OUT_F32, DS_EPI_OUT_PLANES16, DS_EPI_RESIDUAL, DS_EPI_STATS, DS_TAIL_SMALL_MAX_B, NativeLib, PackJob)
 
 PACK_BATCH_MAX = 32                         # DS_PACK_BATCH_MAX (include/deepspeaker_hip.h)
 
@@ -476,12 +476,19 @@ class Engine:
         same stream); input, output and stream are patched into three mutable ctypes slots per call.
 
         `per_layer` (forward_eval): one launch per convolution, channels-last throughout -- no fused BasicBlock
-        kernel, no channel-plane layout; `taps` then receives every stage's three activation buffers."""
+        kernel, no channel-plane layout; `taps` then receives every stage's three activation buffers.
+
+        `low_latency` means what the precision makes of it.  fp16: split-K small launches and the one-launch tail.
+        bf16x3: the stage convolutions are planned under DS_CONV_PLAN_LATENCY -- the same kernel and the same bits through
+        smaller tiles where a launch leaves the chip short of waves; the tail launches stay the ones they are
+        (ds_tail_small_f32 sums in another order).  The other precisions ignore it."""
         B, _, T, F = x.shape
         dev = x.device
         lowp = precision != "f32"
         x3 = precision == "bf16x3"
         h16 = precision == "f16"
+        latency_tiles = low_latency and x3
+        low_latency = low_latency and h16
         x_slot, e_slot, st_slot = ctypes.c_void_p(0), ctypes.c_void_p(0), ctypes.c_void_p(0)
         calls = []            # (raw function, argument tuple, profile label or None, flops)
         keep = []             # tensors / structs the argument tuples point into
@@ -525,7 +532,8 @@ class Engine:
             y = buf(Bc, ho, wo, cout)
             if lowp:
                 args = (ctypes.byref(shp), src_p, self._p(w_bf16[0]), self._p(w_bf16[1]) if x3 else None,
-                        self._p(sc), self._p(sh), self._p(res), self._p(y), None, flags, st_slot)
+                        self._p(sc), self._p(sh), self._p(res), self._p(y), None,
+                        flags | (DS_CONV_PLAN_LATENCY if latency_tiles else 0), st_slot)
                 calls.append((self.lib.raw("ds_conv_fwd_bf16"), args, label, flops))
             else:
                 args = (ctypes.byref(shp), src_p, self._p(w_f32), self._p(sc), self._p(sh), self._p(res), self._p(y),
@@ -654,9 +662,11 @@ class Engine:
         utterance alone (rows past an utterance's extent are re-zeroed after each layer, the temporal mean runs
         over its own rows).
 
-        `low_latency` (fp16 path): launches too small to fill the GPU split their contraction over several
-        workgroups per tile (serving one or a few utterances); results then differ from the one-pass path by the f32
-        summation order."""
+        `low_latency`: plan for the latency of a batch too small to fill the GPU (serving one or a few utterances,
+        the near-tie refinement's slots).  fp16 path: such launches split their contraction over several workgroups
+        per tile; results then differ from the one-pass path by the f32 summation order.  bf16x3 path: such launches
+        run smaller tiles of the same kernel (DS_CONV_PLAN_LATENCY), which shortens every wave's walk over the
+        contraction; results are bit-identical to the default plan's.  Ignored by the other precisions."""
         self._check_eval_args(x, pw, precision)
         # the plan owns its intermediate activations: forwards in flight on different streams need their own
         stream_id = torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else 0
@@ -676,7 +686,7 @@ class Engine:
                       and (q.get("owner") is None or q.get("owner") == owner)]:
                 del plans[k]
             plan = self._build_eval_plan(x, pw, folded, precision, masked=lengths is not None,
-                                         low_latency=low_latency and precision == "f16")
+                                         low_latency=low_latency)
             plan["bytes"] = sum(t.numel() * t.element_size() for t in plan["keep"] if isinstance(t, torch.Tensor))
             plan["owner"] = owner
             # least recently used first (dicts keep insertion order): at most PLAN_CACHE_ENTRIES plans /

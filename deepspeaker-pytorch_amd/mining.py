@@ -51,6 +51,9 @@ PROBE_STRIDE = 37           # the probe window moves by this many triplets per c
 REFINE_CAP_START = 32       # slots while the policy has no history (96 re-embedded rows)
 REFINE_CAP_MIN = 4          # smallest slot count once it has
 REFINE_CAP = REFINE_CAP_START
+# the slot forwards (3 x cap rows, far too few to fill the GPU) are planned for latency: smaller tiles of the same bf16x3
+# kernel, bit-identical results (Engine.forward_eval_planned(low_latency=True)).  The whole-batch fallback is not.
+REFINE_LOW_LATENCY = True
 
 
 def _pow2ceil(v: int) -> int:
@@ -241,7 +244,8 @@ class RefineWindow:
                         if isinstance(v, torch.Tensor):
                             v.record_stream(side)
             st = eng._stream(self.xr)
-            e_ref = eng.forward_eval_planned(self.xr[:len(ents) * 3 * cap], self.pw_ref, self.folded_ref, precision="bf16x3")
+            e_ref = eng.forward_eval_planned(self.xr[:len(ents) * 3 * cap], self.pw_ref, self.folded_ref, precision="bf16x3",
+                                             low_latency=REFINE_LOW_LATENCY)
             for k, en in enumerate(ents):
                 t, a, p, n = en["t"], en["a"], en["p"], en["n"]
                 e_k = e_ref[k * 3 * cap:(k + 1) * 3 * cap]
@@ -505,7 +509,7 @@ def select_triplets(out_a: torch.Tensor, out_p: torch.Tensor, out_n: torch.Tenso
             # copy -- 19 side-stream operations per call instead of 24)
             eng.lib.call("ds_gather_rows3_f32", eng._p(xs[0]), eng._p(xs[1]), eng._p(xs[2]), eng._p(t["amb_idx"]), eng._p(xr), cap,
                          rows, st)
-            e_ref = eng.forward_eval_planned(xr, pw_ref, folded_ref, precision="bf16x3")
+            e_ref = eng.forward_eval_planned(xr, pw_ref, folded_ref, precision="bf16x3", low_latency=REFINE_LOW_LATENCY)
             d_p, d_n = torch.empty_like(t["d_p"]), torch.empty_like(t["d_n"])
             err = torch.empty(5, dtype=torch.float32, device=a.device)
             eng.lib.call("ds_refine_distances_fused_f32", eng._p(e_ref), eng._p(t["amb_idx"]), eng._p(t["amb_count"]), cap,

@@ -71,6 +71,11 @@ extern "C" {
 #define DS_CONV_IN_PLANES16  512 /* fp16 5x5 convolution: x is channel-plane-major [Cin/16][B*H*W][16]: every
                                     16-channel chunk then reads whole 128-byte lines (a 64-channel channels-last
                                     record is one line, of which a chunk would use a quarter)                       */
+#define DS_CONV_PLAN_LATENCY 8192 /* ds_conv_fwd_bf16, bf16x3: a launch too small to put a wave on every SIMD is planned
+                                     for its latency -- the tile that makes a wave's walk over the contraction shortest,
+                                     the one-sub-tile latency rows included -- instead of for the CU time it takes.  The
+                                     result is bit-identical with and without the flag; not with DS_EPI_STATS (whose
+                                     rows are sized by the plan without it)                                            */
 #define DS_CONV_HINT_SINGLE_BUFFER 64  /* fp16 convolution: plan with one LDS pixel tile (tuning / test hint)  */
 #define DS_CONV_HINT_CHUNK16      128  /* fp16 5x5 convolution: plan with 16-channel chunks (tuning / test hint)  */
 #define DS_CONV_HINT_NO_WIDE     2048  /* fp16 convolution: keep 64-channel-wide register tiles where the persistent kernel
@@ -219,6 +224,8 @@ int ds_conv_bf16_stats_rows(const ds_conv_shape *s, int x3);
 /* tiling the bf16 planner picks: out8 = {M tile, N tile, rows per segment, segments per tile, workgroups,
  * LDS bytes, threads per workgroup, LDS row pitch in pixel records} */
 int ds_conv_bf16_plan_describe(const ds_conv_shape *s, int x3, int *out8);
+/* the same under the DS_CONV_PLAN_LATENCY bit of `flags` (what ds_conv_fwd_bf16 would launch) */
+int ds_conv_bf16_plan_describe_hinted(const ds_conv_shape *s, int x3, int flags, int *out8);
 void ds_conv_bf16_set_forced_cfg(int cfg);  /* tuning hook, as ds_conv_f16_set_forced_cfg */
 int ds_conv_fwd_bf16(const ds_conv_shape *s, const float *x, const void *w_hi, const void *w_lo,
                      const float *scale, const float *shift, const float *residual, float *y,
