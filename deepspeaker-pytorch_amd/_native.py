@@ -67,6 +67,7 @@ _SIGNATURES = {
     "ds_conv_out_dims": (c_int, [POINTER(ConvShape), POINTER(c_int), POINTER(c_int)]),
     "ds_conv_stats_rows": (c_int, [POINTER(ConvShape)]),
     "ds_conv_plan_describe": (c_int, [POINTER(ConvShape), POINTER(c_int)]),
+    "ds_conv_f32_set_forced_cfg": (None, [c_int]),
     "ds_conv5x5s2_c1_stats_rows": (c_int, [c_int, c_int]),
     "ds_conv5x5s2_c1_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_conv5x5s2_c1_fwd_bf16": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),

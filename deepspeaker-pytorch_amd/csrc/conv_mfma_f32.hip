@@ -343,6 +343,7 @@ constexpr TileCfg kCfg[kNumCfg] = {
     {160, 128, 256, 1, 2},    // conv_mfma_f32_kernel<KS,5,1,1,4,*>
     {256, 64, 256, 2, 2},     // conv_mfma_f32_kernel<KS,4,1,2,2,*>
 };
+static int g_forced_cfg_f32 = -1;    // test hook (tests/f32_conv_cases.py): plan with this tile configuration only
 
 struct ConvPlan {
     int cfg;
@@ -361,6 +362,7 @@ static int plan_tiles(ConvPlan &pl, int B, int Hr, int Wc, int IS, int ext_h, in
     double best_eff = -1.0;
     int best_cfg = -1, best_rt = 0, best_ni = 0;
     for (int c = 0; c < kNumCfg; ++c) {
+        if (g_forced_cfg_f32 >= 0 && c != g_forced_cfg_f32) continue;
         const TileCfg &cf = kCfg[c];
         if (Cout % cf.NTILE) continue;
         // the whole input tile is staged, halo included: MAX_STAGE_IT float4 slots per thread
@@ -517,6 +519,8 @@ extern "C" int ds_conv_dgrad_f32(const ds_conv_shape *s, const float *gy, const 
     }
     return DS_OK;
 }
+
+extern "C" void ds_conv_f32_set_forced_cfg(int cfg) { g_forced_cfg_f32 = (cfg >= 0 && cfg < kNumCfg) ? cfg : -1; }
 
 extern "C" int ds_conv_plan_describe(const ds_conv_shape *s, int *out8) {
     DS_REQUIRE(out8, DS_ERR_NULL);

@@ -26,8 +26,8 @@
  *       (2) the armed event pair of ds_launch_timing_arm: thread-local, consumed by
  *           the calling thread's next MFMA launch (csrc/ds_device.h);
  *       (3) process-wide tuning hooks, ds_conv_f16_set_layout_padding and
- *           ds_conv_{f16,bf16}_set_forced_cfg (off by default; A/B hooks that change speed,
- *           never results);
+ *           ds_conv_{f32,f16,bf16}_set_forced_cfg (off by default; A/B and test hooks that
+ *           change speed, never results);
  *       (4) the cached compute-unit count per device (read once).
  *     Nothing else is kept between calls.
  *   - return value: 0 = DS_OK, negative = argument error (below), positive = the
@@ -186,6 +186,9 @@ int ds_conv_stats_rows(const ds_conv_shape *s);
 /* tiling the planner picks for a shape: out8 = {M tile, N tile, rows per segment, segments per tile,
  * workgroups, LDS bytes, staging slots per thread, M tiles} (introspection for tests / DESIGN.md) */
 int ds_conv_plan_describe(const ds_conv_shape *s, int *out8);
+/* test hook, as ds_conv_f16_set_forced_cfg: plan the f32 forward and both data gradients with tile configuration `cfg`
+ * only (0: 128x64, 1: 160x128, 2: 256x64; anything else: the planner's choice) */
+void ds_conv_f32_set_forced_cfg(int cfg);
 int ds_conv5x5s2_c1_stats_rows(int B, int H);
 /* conv1: 5x5 stride 2 pad 2, Cin = 1 -> 64 channels (model.py:93,187) fused with the following
  * BatchNorm affine + clipped ReLU (model.py:188-189).  x is the network input [B,H,W]. */
