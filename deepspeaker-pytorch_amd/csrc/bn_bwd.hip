@@ -1,6 +1,7 @@
 // bn_bwd.hip -- backward of train-mode BatchNorm (f32 class: the f32 and bf16x3 training steps) for a batch of G members
 // with their own statistics (one member: G = 1), its split forms for data parallelism (float64 sums between the
-// reduction and the application, forward and backward) and the column sum of the fc bias gradient.
+// reduction and the application), the float64 fold of partial rows (forward and backward) and the column sum of the
+// fc bias gradient.
 #include <ds_device.h>
 #include "ds_common.h"
 #include "bn_fold.h"
@@ -55,6 +56,9 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const float *g1, con
             s1 += g;
             s2 += g * xh;
         }
+        // From here on this restates block_fold<4> of bn_fold.h (red, s1, s2, slot, slots, cg, C, partial), written out:
+        // calling it gives the same 335 instructions with other registers and another schedule around the loop, and
+        // this is the one hot kernel of the file -- its text stays what was measured.  Change the two together.
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             red[((slot * C) + cg * 4 + j) * 2 + 0] = s1[j];
@@ -81,7 +85,7 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_group_kernel(const float 
                                                                     const float *gamma, const float *invstd,
                                                                     float *ggamma_m, float *gbeta_m, float *coef, int C,
                                                                     int n_cgroups) {
-    double *red = (double *)ds_dynamic_lds();              // [FOLD_R][FOLD_C][2]
+    double *red = (double *)ds_dynamic_lds();              // [4 waves][FOLD_C][2] (128 of the bytes the launch asks for)
     const int member = blockIdx.x / n_cgroups, cgroup = blockIdx.x - member * n_cgroups;
     partial += (size_t)member * n_partial * C * 2;
     invstd += (size_t)member * C;
@@ -91,9 +95,7 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_group_kernel(const float 
     if (fold_partials(partial, n_partial, C, red, c, t1, t2, cgroup)) {
         gbeta_m[(size_t)member * C + c] = (float)t1;
         ggamma_m[(size_t)member * C + c] = (float)t2;
-        coef[c] = gamma[c] * invstd[c];
-        coef[C + c] = (float)(t1 / count);
-        coef[2 * C + c] = (float)(t2 / count);
+        bn_bwd_store_coef(coef, C, c, gamma[c], invstd[c], t1, t2, count);
     }
 }
 
@@ -153,32 +155,8 @@ __global__ void __launch_bounds__(256) colsum_kernel(const float *x, float *out,
 
 }  // namespace
 
-// ---- split forms for data-parallel training: local sums -> (all-reduce by the caller) -> finalize ----
+// ---- split forms for data-parallel training: local sums -> (all-reduce by the caller) -> finish ----
 namespace {
-
-__global__ void __launch_bounds__(256) bn_stats_from_sums_kernel(const double *sums, double count, const float *gamma,
-                                                                 const float *beta, float eps, float momentum,
-                                                                 float *running_mean, float *running_var,
-                                                                 float *batch_mean, float *batch_invstd, float *scale,
-                                                                 float *shift, int C) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    if (count <= 0.0) count = sums[2 * C];               // pixel count travelled with the all-reduce
-    const double mean = sums[c * 2] / count;
-    double var = sums[c * 2 + 1] / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double invstd = 1.0 / sqrt(var + (double)eps);
-    const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-    if (running_mean) {
-        running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
-        running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unbiased);
-    }
-    if (batch_mean) batch_mean[c] = (float)mean;
-    if (batch_invstd) batch_invstd[c] = (float)invstd;
-    const double sc = (double)gamma[c] * invstd;
-    scale[c] = (float)sc;
-    shift[c] = (float)((double)beta[c] - mean * sc);
-}
 
 // Partial rows -> float64 sums, folded like the single-process finalize kernels fold them (fold_partials: FOLD_C
 // channels x FOLD_R row lanes per workgroup; one workgroup per 32 channels with 8 row lanes left 6..48 workgroups
@@ -188,7 +166,7 @@ __global__ void __launch_bounds__(256) bn_stats_from_sums_kernel(const double *s
 // written (ds_partial_sum_f64 promises [C][2]).
 __global__ void __launch_bounds__(256) partial_sum_f64_group_kernel(const float *partial, int n_partial, double *sums,
                                                                     double count, int C, int n_cgroups) {
-    double *red = (double *)ds_dynamic_lds();              // [FOLD_R][FOLD_C][2]
+    double *red = (double *)ds_dynamic_lds();              // [4 waves][FOLD_C][2] (128 of the bytes the launch asks for)
     const int member = blockIdx.x / n_cgroups, cgroup = blockIdx.x - member * n_cgroups;
     partial += (size_t)member * n_partial * C * 2;
     sums += (size_t)member * (2 * C + 1);
@@ -215,9 +193,7 @@ __global__ void __launch_bounds__(256) bn_bwd_from_sums_group_kernel(const doubl
     if (count <= 0.0) count = sums[2 * C];
     gbeta_m[(size_t)member * C + c] = (float)sums[c * 2];
     ggamma_m[(size_t)member * C + c] = (float)sums[c * 2 + 1];
-    coef[c] = gamma[c] * invstd[c];
-    coef[C + c] = (float)(sums[c * 2] / count);
-    coef[2 * C + c] = (float)(sums[c * 2 + 1] / count);
+    bn_bwd_store_coef(coef, C, c, gamma[c], invstd[c], sums[c * 2], sums[c * 2 + 1], count);
 }
 
 // ---- the stages on the host side, every launch written once ----
@@ -289,7 +265,8 @@ extern "C" int ds_bn_bwd_partial_rows(long long n_pix, int C) {
     return (int)blocks;
 }
 
-// ---- forward statistics of data-parallel training: local sums -> (all-reduce by the caller) -> finalize ----
+// ---- the float64 folds of data-parallel training, forward and backward (the forward's second half,
+// ds_bn_stats_from_sums_f32, is with the other forward statistics in bn_pack.hip) ----
 // sums [C][2] float64 of one member's partial rows: ds_partial_sum_f64_group with G = 1, minus the count slot
 extern "C" int ds_partial_sum_f64(const float *partial, int n_partial, double *sums, int C, void *stream) {
     DS_REQUIRE(partial && sums, DS_ERR_NULL);
@@ -304,18 +281,6 @@ extern "C" int ds_partial_sum_f64_group(const float *partial, int n_partial, dou
     DS_REQUIRE(partial && sums, DS_ERR_NULL);
     DS_REQUIRE(n_partial > 0 && C > 0 && G > 0 && G <= 64 && count > 0, DS_ERR_BAD_SHAPE);
     return fold_to_sums(partial, n_partial, sums, (double)count, C, G, stream);
-}
-
-extern "C" int ds_bn_stats_from_sums_f32(const double *sums, long long count, const float *gamma, const float *beta,
-                                         float eps, float momentum, float *running_mean, float *running_var,
-                                         float *batch_mean, float *batch_invstd, float *scale, float *shift, int C,
-                                         void *stream) {
-    DS_REQUIRE(sums && gamma && beta && scale && shift, DS_ERR_NULL);
-    DS_REQUIRE((running_mean == nullptr) == (running_var == nullptr), DS_ERR_NULL);
-    DS_REQUIRE(C > 0 && count >= 0, DS_ERR_BAD_SHAPE);
-    DS_LAUNCH(bn_stats_from_sums_kernel, ds_ceil_div(C, 256), 256, 0, stream, sums, (double)count, gamma, beta, eps,
-              momentum, running_mean, running_var, batch_mean, batch_invstd, scale, shift, C);
-    return ds_last_launch_error();
 }
 
 // ---- the backward of one member: the G = 1 case of the grouped forms below (three launches) ----

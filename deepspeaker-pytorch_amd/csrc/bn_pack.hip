@@ -1,9 +1,10 @@
 // bn_pack.hip -- forward BatchNorm bookkeeping kernels and one-off layout/weight packing.
-//   * eval-mode fold and train-mode statistics finalisation of nn.BatchNorm2d
-//     (reference model.py:59,62,94,99,103,107; semantics SURVEY 8(a) a2)
+//   * eval-mode fold and train-mode statistics finalisation of nn.BatchNorm2d, for one member or G, from partial rows
+//     or from float64 sums (reference model.py:59,62,94,99,103,107; semantics SURVEY 8(a) a2): every forward
+//     statistics kernel of the library, the fp16 step's included
 //   * elementwise normalise (+residual, +clipped ReLU) for the train-mode path
 //   * OIHW -> packed filter layouts, NCHW <-> channels-last conversion
-// (BatchNorm's backward, the float64 split forms, the scheduler pool and the ABI version are in files of their own.)
+// (BatchNorm's backward, the float64 folds, the scheduler pool and the ABI version are in files of their own.)
 #include <ds_device.h>
 #include "ds_common.h"
 #include "bn_fold.h"
@@ -22,30 +23,47 @@ __global__ void __launch_bounds__(256) bn_fold_kernel(const float *gamma, const 
     }
 }
 
-__global__ void __launch_bounds__(256) bn_stats_finalize_kernel(const float *partial, int n_partial, double count,
-                                                                const float *gamma, const float *beta, float eps,
-                                                                float momentum, float *running_mean,
-                                                                float *running_var, float *batch_mean,
-                                                                float *batch_invstd, float *scale, float *shift,
-                                                                int C) {
-    double *red = (double *)ds_dynamic_lds();              // [FOLD_R][FOLD_C][2]
-    int c;
-    double t1, t2;
-    if (fold_partials(partial, n_partial, C, red, c, t1, t2)) {
-        const double mean = t1 / count;
-        double var = t2 / count - mean * mean;             // biased (normalisation) variance
-        if (var < 0.0) var = 0.0;
-        const double invstd = 1.0 / sqrt(var + (double)eps);
-        const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-        if (running_mean) {
-            running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
-            running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unbiased);
+__device__ __forceinline__ float *at_or_null(float *p, size_t i) { return p ? p + i : nullptr; }
+
+// Train-mode statistics of G members of one BatchNorm layer in one launch (one member: G = 1), from partial rows or
+// from float64 sums: batch mean / invstd / (scale, shift) per member into [G][C] tables (mean_t / invstd_t may be
+// null), and the running statistics updated member after member IN CALL ORDER (the reference's model(data_a),
+// model(data_p), model(data_n) are three nn.BatchNorm2d.train() calls: three momentum updates, model.py:188).
+__global__ void __launch_bounds__(256) bn_stats_finalize_group_kernel(const float *partial, int n_partial, double count,
+                                                                      const float *gamma, const float *beta, float eps,
+                                                                      float momentum, float *running_mean,
+                                                                      float *running_var, float *mean_t, float *invstd_t,
+                                                                      float *scale_t, float *shift_t, int C, int G) {
+    double *red = (double *)ds_dynamic_lds();              // [4 waves][FOLD_C][2] (128 of the bytes the launch asks for)
+    for (int m = 0; m < G; ++m) {
+        if (m) __syncthreads();                             // (the previous member's fold has been read)
+        int c;
+        double t1, t2;
+        if (fold_partials(partial + (size_t)m * n_partial * C * 2, n_partial, C, red, c, t1, t2)) {
+            const size_t o = (size_t)m * C + c;
+            bn_stats_of_channel(t1, t2, count, gamma[c], beta[c], eps, momentum, at_or_null(running_mean, c),
+                                at_or_null(running_var, c), at_or_null(mean_t, o), at_or_null(invstd_t, o), scale_t + o,
+                                shift_t + o);
         }
-        if (batch_mean) batch_mean[c] = (float)mean;
-        if (batch_invstd) batch_invstd[c] = (float)invstd;
-        const double s = (double)gamma[c] * invstd;
-        scale[c] = (float)s;
-        shift[c] = (float)((double)beta[c] - mean * s);
+    }
+}
+
+// ... from sums [G][2C+1] float64 (per member C pairs { sum z, sum z^2 } and the pixel count, which travels with the
+// all-reduce of data-parallel training); count > 0 overrides the count slot, which is then not read (G = 1: the
+// sums may be [C][2] alone)
+__global__ void __launch_bounds__(256) bn_stats_from_sums_group_kernel(const double *sums, double count,
+                                                                       const float *gamma, const float *beta, float eps,
+                                                                       float momentum, float *running_mean,
+                                                                       float *running_var, float *mean_t, float *invstd_t,
+                                                                       float *scale_t, float *shift_t, int C, int G) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    for (int m = 0; m < G; ++m) {
+        const double *sm = sums + (size_t)m * (2 * C + 1);
+        const size_t o = (size_t)m * C + c;
+        bn_stats_of_channel(sm[c * 2], sm[c * 2 + 1], count > 0.0 ? count : sm[2 * C], gamma[c], beta[c], eps, momentum,
+                            at_or_null(running_mean, c), at_or_null(running_var, c), at_or_null(mean_t, o),
+                            at_or_null(invstd_t, o), scale_t + o, shift_t + o);
     }
 }
 
@@ -189,7 +207,27 @@ __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float *x, float
     }
 }
 
+// the one launch of the sums form (no argument checks: the two entry points keep their own)
+int stats_from_sums(const double *sums, double count, const float *gamma, const float *beta, float eps, float momentum,
+                    float *running_mean, float *running_var, float *mean_t, float *invstd_t, float *scale_t,
+                    float *shift_t, int C, int G, void *stream) {
+    DS_LAUNCH(bn_stats_from_sums_group_kernel, ds_ceil_div(C, 256), 256, 0, stream, sums, count, gamma, beta, eps, momentum,
+              running_mean, running_var, mean_t, invstd_t, scale_t, shift_t, C, G);
+    return ds_last_launch_error();
+}
+
 }  // namespace
+
+// ... and of the rows form (bn_fold.h).  The fold uses 4 waves x FOLD_C x 2 doubles of the LDS it asks for; the
+// request is what these launches have always made.
+int ds_bn_launch_stats_finalize(const float *partial, int n_partial, double count, const float *gamma, const float *beta,
+                                float eps, float momentum, float *running_mean, float *running_var, float *mean_t,
+                                float *invstd_t, float *scale_t, float *shift_t, int C, int G, void *stream) {
+    DS_LAUNCH(bn_stats_finalize_group_kernel, ds_ceil_div(C, FOLD_C), 256, FOLD_R * FOLD_C * 2 * sizeof(double), stream,
+              partial, n_partial, count, gamma, beta, eps, momentum, running_mean, running_var, mean_t, invstd_t, scale_t,
+              shift_t, C, G);
+    return ds_last_launch_error();
+}
 
 extern "C" int ds_bn_fold_f32(const float *gamma, const float *beta, const float *running_mean,
                               const float *running_var, float eps, float *scale, float *shift, int C, void *stream) {
@@ -207,10 +245,33 @@ extern "C" int ds_bn_stats_finalize_f32(const float *partial, int n_partial, lon
     DS_REQUIRE(partial && gamma && beta && scale && shift, DS_ERR_NULL);
     DS_REQUIRE((running_mean == nullptr) == (running_var == nullptr), DS_ERR_NULL);
     DS_REQUIRE(C > 0 && n_partial > 0 && count > 0, DS_ERR_BAD_SHAPE);
-    DS_LAUNCH(bn_stats_finalize_kernel, ds_ceil_div(C, FOLD_C), 256, FOLD_R * FOLD_C * 2 * sizeof(double), stream, partial,
-              n_partial, (double)count, gamma, beta, eps, momentum, running_mean, running_var, batch_mean,
-              batch_invstd, scale, shift, C);
-    return ds_last_launch_error();
+    return ds_bn_launch_stats_finalize(partial, n_partial, (double)count, gamma, beta, eps, momentum, running_mean,
+                                       running_var, batch_mean, batch_invstd, scale, shift, C, 1, stream);
+}
+
+// ---- forward statistics of data-parallel training: local sums -> (all-reduce by the caller) -> finalize ----
+// one member from sums [C][2] and its count, or (count == 0) from sums [2C+1] with the count in the last slot
+extern "C" int ds_bn_stats_from_sums_f32(const double *sums, long long count, const float *gamma, const float *beta,
+                                         float eps, float momentum, float *running_mean, float *running_var,
+                                         float *batch_mean, float *batch_invstd, float *scale, float *shift, int C,
+                                         void *stream) {
+    DS_REQUIRE(sums && gamma && beta && scale && shift, DS_ERR_NULL);
+    DS_REQUIRE((running_mean == nullptr) == (running_var == nullptr), DS_ERR_NULL);
+    DS_REQUIRE(C > 0 && count >= 0, DS_ERR_BAD_SHAPE);
+    return stats_from_sums(sums, (double)count, gamma, beta, eps, momentum, running_mean, running_var, batch_mean,
+                           batch_invstd, scale, shift, C, 1, stream);
+}
+
+// [G][C] tables (and the running statistics, members in call order) from the all-reduced sums [G][2C+1] of G members:
+// the second half of ds_bn_stats_partial_f16 + ds_partial_sum_f64_group
+extern "C" int ds_bn_stats_from_sums_group_f32(const double *sums, const float *gamma, const float *beta, float eps,
+                                               float momentum, float *running_mean, float *running_var, float *mean_t,
+                                               float *invstd_t, float *scale_t, float *shift_t, int C, int G, void *stream) {
+    DS_REQUIRE(sums && gamma && beta && mean_t && invstd_t && scale_t && shift_t, DS_ERR_NULL);
+    DS_REQUIRE(C > 0 && G > 0 && G <= 64, DS_ERR_BAD_SHAPE);
+    DS_REQUIRE((running_mean == nullptr) == (running_var == nullptr), DS_ERR_NULL);
+    return stats_from_sums(sums, 0.0, gamma, beta, eps, momentum, running_mean, running_var, mean_t, invstd_t, scale_t,
+                           shift_t, C, G, stream);
 }
 
 extern "C" int ds_bn_apply_f32(const float *x, const float *scale, const float *shift, const float *residual,

@@ -14,6 +14,7 @@
 // statistics: member m owns pixels [m * n_pix, (m + 1) * n_pix) and row m of every [G][C] table.
 #include <ds_device.h>
 #include "ds_common.h"
+#include "bn_fold.h"
 #include <stdlib.h>
 
 namespace {
@@ -35,30 +36,7 @@ __device__ __forceinline__ void st8f(float *p, size_t i8, f32x8 v) {
     ((f32x4 *)p)[2 * i8 + 1] = f32x4{v[4], v[5], v[6], v[7]};
 }
 
-constexpr int TF_FOLD_R = 128, TF_FOLD_C = 2;   // row lanes x channels per workgroup of the partial-sum folds below
 constexpr int TF_MAX_ROWS = 768;                // partial rows per member (x G members: enough workgroups, short folds)
-
-// per-block partial sums of two per-channel quantities -> partial[blockIdx.x][c][2]; red: [slots][C][2] floats
-__device__ __forceinline__ void block_fold(float *red, const f32x8 &s1, const f32x8 &s2, int slot, int slots, int cg, int C,
-                                           float *partial) {
-    if (slot < slots) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            red[((slot * C) + cg * 8 + j) * 2 + 0] = s1[j];
-            red[((slot * C) + cg * 8 + j) * 2 + 1] = s2[j];
-        }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float a1 = 0.f, a2 = 0.f;
-        for (int s = 0; s < slots; ++s) {
-            a1 += red[(s * C + c) * 2 + 0];
-            a2 += red[(s * C + c) * 2 + 1];
-        }
-        partial[((size_t)blockIdx.x * C + c) * 2 + 0] = a1;
-        partial[((size_t)blockIdx.x * C + c) * 2 + 1] = a2;
-    }
-}
 
 // partial[member][blk][c] = { sum z, sum z^2 } over the block's pixels (f32 sums of fp16 values)
 __global__ void __launch_bounds__(256) bn_stats_f16_kernel(const h16 *z, float *partial, long long n_pix, int C,
@@ -80,77 +58,7 @@ __global__ void __launch_bounds__(256) bn_stats_f16_kernel(const h16 *z, float *
             s1 += v;
             s2 += v * v;
         }
-    block_fold(red, s1, s2, slot, slots, cg, C, partial);
-}
-
-// fold of one member's partial rows for TF_FOLD_C channels per workgroup, double precision, fixed order: a thread adds
-// its rows (rl, rl + TF_FOLD_R, ...), the 32 row lanes of a wave are folded by an xor tree of shuffles (lane = 2 rl + cl:
-// offsets 2 .. 32), the four waves' results meet in LDS.  (Round 6: the last step used to be ONE thread adding 128 LDS
-// values per channel and member in sequence -- 16 - 35 us for a launch that moves a few hundred KB, 24 of them on the
-// critical path of every fp16 training step.)
-__device__ __forceinline__ bool fold_rows(const float *partial, int n_partial, int C, double *red, int c0, int &c, double &t1,
-                                          double &t2) {
-    static_assert(TF_FOLD_C == 2 && TF_FOLD_R == 128, "lane = 2 * row lane + channel; four waves");
-    const int cl = threadIdx.x % TF_FOLD_C, rl = threadIdx.x / TF_FOLD_C;
-    c = c0 + cl;
-    double s1 = 0.0, s2 = 0.0;
-    if (c < C)
-        for (int r = rl; r < n_partial; r += TF_FOLD_R) {
-            const float *src = partial + ((size_t)r * C + c) * 2;
-            s1 += (double)src[0];
-            s2 += (double)src[1];
-        }
-#pragma unroll
-    for (int m = 2; m <= 32; m <<= 1) {
-        s1 += ds_shfl_xor_f64(s1, m);
-        s2 += ds_shfl_xor_f64(s2, m);
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();                                        // (the previous member's fold has been read)
-    if (lane < TF_FOLD_C) {
-        red[(wave * TF_FOLD_C + cl) * 2 + 0] = s1;
-        red[(wave * TF_FOLD_C + cl) * 2 + 1] = s2;
-    }
-    __syncthreads();
-    if (rl != 0 || c >= C) return false;
-    t1 = t2 = 0.0;
-    for (int k = 0; k < 4; ++k) {
-        t1 += red[(k * TF_FOLD_C + cl) * 2 + 0];
-        t2 += red[(k * TF_FOLD_C + cl) * 2 + 1];
-    }
-    return true;
-}
-
-// All G members of one BatchNorm layer in one launch: batch mean / invstd / (scale, shift) per member into [G][C]
-// tables, and the running statistics updated member after member IN CALL ORDER (the reference's model(data_a),
-// model(data_p), model(data_n) are three nn.BatchNorm2d.train() calls: three momentum updates, model.py:188).
-__global__ void __launch_bounds__(256) bn_stats_finalize_group_kernel(const float *partial, int n_partial, double count,
-                                                                      const float *gamma, const float *beta, float eps,
-                                                                      float momentum, float *running_mean,
-                                                                      float *running_var, float *mean_t, float *invstd_t,
-                                                                      float *scale_t, float *shift_t, int C, int G) {
-    double *red = (double *)ds_dynamic_lds();              // [TF_FOLD_R][TF_FOLD_C][2]
-    for (int m = 0; m < G; ++m) {
-        int c;
-        double t1, t2;
-        if (fold_rows(partial + (size_t)m * n_partial * C * 2, n_partial, C, red, (int)blockIdx.x * TF_FOLD_C, c, t1, t2)) {
-            const double mean = t1 / count;
-            double var = t2 / count - mean * mean;         // biased (normalisation) variance
-            if (var < 0.0) var = 0.0;
-            const double invstd = 1.0 / sqrt(var + (double)eps);
-            const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-            if (running_mean) {
-                running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
-                running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unbiased);
-            }
-            const size_t o = (size_t)m * C + c;
-            mean_t[o] = (float)mean;
-            invstd_t[o] = (float)invstd;
-            const double s = (double)gamma[c] * invstd;
-            scale_t[o] = (float)s;
-            shift_t[o] = (float)((double)beta[c] - mean * s);
-        }
-    }
+    block_fold<8>(red, s1, s2, slot, slots, cg, C, partial);
 }
 
 // Element-wise passes walk [G members][n_vec_member] 8-channel vectors.  256 threads per workgroup and a channel-group
@@ -261,7 +169,7 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_f16_kernel(const h16 *g1, c
             s2 += g * ((zv - mu) * is);
         }
     }
-    block_fold(red, s1, s2, slot, slots, cg, C, partial);
+    block_fold<8>(red, s1, s2, slot, slots, cg, C, partial);
 }
 
 // Backward, fold: per member coef = { gamma * invstd, sum gy / N, sum gy * xhat / N } (in the gradient tensors' scaled
@@ -270,18 +178,16 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_f16_kernel(const float *p
                                                                   const float *gamma, const float *invstd_t, float *coef,
                                                                   float *ggamma, float *gbeta, int C, int G,
                                                                   float inv_scale) {
-    double *red = (double *)ds_dynamic_lds();
+    double *red = (double *)ds_dynamic_lds();              // [4 waves][FOLD_C][2] (128 of the bytes the launch asks for)
     double gg = 0.0, gb = 0.0;
     int c = 0;
     bool mine = false;
     for (int m = 0; m < G; ++m) {
+        if (m) __syncthreads();                             // (the previous member's fold has been read)
         double t1, t2;
-        if (fold_rows(partial + (size_t)m * n_partial * C * 2, n_partial, C, red, (int)blockIdx.x * TF_FOLD_C, c, t1, t2)) {
+        if (fold_partials(partial + (size_t)m * n_partial * C * 2, n_partial, C, red, c, t1, t2)) {
             mine = true;
-            float *cf = coef + (size_t)m * 3 * C;
-            cf[c] = gamma[c] * invstd_t[(size_t)m * C + c];
-            cf[C + c] = (float)(t1 / count);
-            cf[2 * C + c] = (float)(t2 / count);
+            bn_bwd_store_coef(coef + (size_t)m * 3 * C, C, c, gamma[c], invstd_t[(size_t)m * C + c], t1, t2, count);
             gb += (double)(float)t1;                        // (the f32 path adds the members' f32 sums)
             gg += (double)(float)t2;
         }
@@ -289,35 +195,6 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_f16_kernel(const float *p
     if (mine) {
         ggamma[c] = (float)(gg * (double)inv_scale);
         gbeta[c] = (float)(gb * (double)inv_scale);
-    }
-}
-
-// data-parallel forward: the [G][2C+1] float64 sums (per member C pairs { sum z, sum z^2 } and the pixel count) have been
-// all-reduced over the ranks; tables per member, running statistics member after member (call order) -- one launch
-__global__ void __launch_bounds__(256) bn_stats_from_sums_group_kernel(const double *sums, const float *gamma, const float *beta,
-                                                                       float eps, float momentum, float *running_mean,
-                                                                       float *running_var, float *mean_t, float *invstd_t,
-                                                                       float *scale_t, float *shift_t, int C, int G) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    for (int m = 0; m < G; ++m) {
-        const double *sm = sums + (size_t)m * (2 * C + 1);
-        const double count = sm[2 * C];
-        const double mean = sm[c * 2] / count;
-        double var = sm[c * 2 + 1] / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const double invstd = 1.0 / sqrt(var + (double)eps);
-        const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-        if (running_mean) {
-            running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
-            running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unbiased);
-        }
-        const size_t o = (size_t)m * C + c;
-        mean_t[o] = (float)mean;
-        invstd_t[o] = (float)invstd;
-        const double sc = (double)gamma[c] * invstd;
-        scale_t[o] = (float)sc;
-        shift_t[o] = (float)((double)beta[c] - mean * sc);
     }
 }
 
@@ -331,11 +208,8 @@ __global__ void __launch_bounds__(256) bn_bwd_from_sums_f16_kernel(const double 
     double gg = 0.0, gb = 0.0;
     for (int m = 0; m < G; ++m) {
         const double *sm = sums + (size_t)m * (2 * C + 1);
-        const double count = sm[2 * C];
-        float *cf = coef + (size_t)m * 3 * C;
-        cf[c] = gamma[c] * invstd_t[(size_t)m * C + c];
-        cf[C + c] = (float)(sm[c * 2] / count);
-        cf[2 * C + c] = (float)(sm[c * 2 + 1] / count);
+        bn_bwd_store_coef(coef + (size_t)m * 3 * C, C, c, gamma[c], invstd_t[(size_t)m * C + c], sm[c * 2], sm[c * 2 + 1],
+                          sm[2 * C]);
         gb += (double)(float)sm[c * 2];
         gg += (double)(float)sm[c * 2 + 1];
     }
@@ -432,15 +306,14 @@ extern "C" int ds_bn_stats_group_f16(const void *z_f16, float *partial, long lon
               ppb, blocks);
     int rc = ds_last_launch_error();
     if (rc) return rc;
-    DS_LAUNCH(bn_stats_finalize_group_kernel, ds_ceil_div(C, TF_FOLD_C), 256, TF_FOLD_R * TF_FOLD_C * 2 * sizeof(double), stream,
-              (const float *)partial, blocks, (double)n_pix, gamma, beta, eps, momentum, running_mean, running_var, mean_t,
-              invstd_t, scale_t, shift_t, C, G);
-    return ds_last_launch_error();
+    return ds_bn_launch_stats_finalize(partial, blocks, (double)n_pix, gamma, beta, eps, momentum, running_mean, running_var,
+                                       mean_t, invstd_t, scale_t, shift_t, C, G, stream);
 }
 
 // Data-parallel split of the above (one process per GPU): only the partial sums { sum z, sum z^2 } per member.  The caller
 // folds them to float64 (ds_partial_sum_f64_group, n_partial = ds_bn_f16_partial_rows), all-reduces the [G][2C+1] sums over
-// RCCL and finishes each member with ds_bn_stats_from_sums_f32: every rank normalises with the GLOBAL batch's statistics.
+// RCCL and finishes with ds_bn_stats_from_sums_group_f32 (bn_pack.hip): every rank normalises with the GLOBAL batch's
+// statistics.
 extern "C" int ds_bn_stats_partial_f16(const void *z_f16, float *partial, long long n_pix, int C, int G, void *stream) {
     DS_REQUIRE(z_f16 && partial, DS_ERR_NULL);
     DS_REQUIRE(tf_shape_ok(n_pix, C, G), DS_ERR_BAD_SHAPE);
@@ -450,18 +323,6 @@ extern "C" int ds_bn_stats_partial_f16(const void *z_f16, float *partial, long l
     const int slots = 256 / (C / 8);
     DS_LAUNCH(bn_stats_f16_kernel, blocks * G, 256, (size_t)slots * C * 2 * 4, stream, (const h16 *)z_f16, partial, n_pix, C,
               ppb, blocks);
-    return ds_last_launch_error();
-}
-
-// ... and the second half: [G][C] tables (and the running statistics, members in call order) from the all-reduced sums
-extern "C" int ds_bn_stats_from_sums_group_f32(const double *sums, const float *gamma, const float *beta, float eps,
-                                               float momentum, float *running_mean, float *running_var, float *mean_t,
-                                               float *invstd_t, float *scale_t, float *shift_t, int C, int G, void *stream) {
-    DS_REQUIRE(sums && gamma && beta && mean_t && invstd_t && scale_t && shift_t, DS_ERR_NULL);
-    DS_REQUIRE(C > 0 && G > 0 && G <= 64, DS_ERR_BAD_SHAPE);
-    DS_REQUIRE((running_mean == nullptr) == (running_var == nullptr), DS_ERR_NULL);
-    DS_LAUNCH(bn_stats_from_sums_group_kernel, ds_ceil_div(C, 256), 256, 0, stream, sums, gamma, beta, eps, momentum, running_mean,
-              running_var, mean_t, invstd_t, scale_t, shift_t, C, G);
     return ds_last_launch_error();
 }
 
@@ -546,7 +407,7 @@ extern "C" int ds_bn_bwd_group_f16(const void *g1, int g1_parity, const void *g2
     int rc = bwd_reduce_f16(g1, g1_parity, g2, act, act_is_f32, mask_scale_t, mask_shift_t, z, mean_t, invstd_t, gy, partial,
                             n_pix, H, W, C, G, stream);
     if (rc) return rc;
-    DS_LAUNCH(bn_bwd_finalize_f16_kernel, ds_ceil_div(C, TF_FOLD_C), 256, TF_FOLD_R * TF_FOLD_C * 2 * sizeof(double), stream,
+    DS_LAUNCH(bn_bwd_finalize_f16_kernel, ds_ceil_div(C, FOLD_C), 256, FOLD_R * FOLD_C * 2 * sizeof(double), stream,
               (const float *)partial, tf_rows(n_pix, C), (double)n_pix, gamma, invstd_t, coef, ggamma, gbeta, C, G, inv_scale);
     rc = ds_last_launch_error();
     if (rc) return rc;

@@ -475,7 +475,8 @@ BN_FWD_CASES = [(5, 8, 128, 10, 4, 3, 1), (2, 8, 64, 9, 32, 3, 1), (3, 16, 128, 
 
 def body_bn_forward(be, case):
     """statistics rows of a real ds_conv_fwd_f32 launch -> ds_bn_stats_finalize_f32 -> ds_bn_apply_f32 -> ds_bn_fold_f32;
-    ds_partial_sum_f64 + ds_bn_stats_from_sums_f32 give the same tables bit for bit"""
+    ds_partial_sum_f64 + ds_bn_stats_from_sums_f32 give the same tables bit for bit, ds_bn_stats_from_sums_group_f32 those
+    of three single calls; the rows form once more on synthetic rows (1 / 129 / 300 of them, part-full last workgroups)"""
     lib, p = be.lib, be.p
     b, ci, co, h, w, k, s = case
     ho, wo = out_dims(h, w, k, s)
@@ -508,6 +509,30 @@ def body_bn_forward(be, case):
                  co, be.stream)
         for a, c in zip(t1 + [rm1, rv1], t2 + [rm2, rv2]):
             assert be.same(a, c), f"split form, count {count}"
+    # the sums form of G = 3 members in one launch against three single calls (count 0: each row's own count slot),
+    # the running statistics chained in call order; once without running statistics
+    rs3 = np.random.RandomState(seed_of(*case) + 3)
+    sums3 = np.empty((3, 2 * co + 1), F64)
+    for m in range(3):
+        zs = rs3.randn(37 + 11 * m, co) * (1 + m) + m
+        sums3[m, :2 * co] = np.stack([zs.sum(0), (zs * zs).sum(0)], axis=1).ravel()
+        sums3[m, 2 * co] = zs.shape[0]
+    s3, s1 = be.put(sums3), [be.put(sums3[m:m + 1]) for m in range(3)]
+    for with_running in (True, False):
+        tg = [be.nan((3, co), F32) for _ in range(4)]
+        ts = [[be.nan((1, co), F32) for _ in range(4)] for m in range(3)]
+        rg = [be.put(rm), be.put(rv)] if with_running else [None, None]
+        rc = [be.put(rm), be.put(rv)] if with_running else [None, None]
+        lib.call("ds_bn_stats_from_sums_group_f32", p(s3), p(g_d), p(b_d), EPS, MOMENTUM, p(rg[0]), p(rg[1]), *(p(t) for t in tg),
+                 co, 3, be.stream)
+        for m in range(3):
+            lib.call("ds_bn_stats_from_sums_f32", p(s1[m]), 0, p(g_d), p(b_d), EPS, MOMENTUM, p(rc[0]), p(rc[1]),
+                     *(p(t) for t in ts[m]), co, be.stream)
+            for a, c in zip(tg, ts[m]):
+                assert np.isfinite(be.get(c)).all() and be.same(be.part(a, m, 1), c), f"grouped sums form, member {m}"
+        if with_running:
+            assert be.same(rg[0], rc[0]) and be.same(rg[1], rc[1]), "grouped sums form, running statistics"
+            assert np.isfinite(be.get(rg[0])).all() and np.isfinite(be.get(rg[1])).all()
     mean_k, invstd_k, scale_k, shift_k = (be.get(t) for t in t1)
     # float64 reference and the float32 restatement (torch float32 convolution, float32 sums per statistics row)
     z64 = O.conv2d(x.astype(F64), wt.astype(F64), s, k // 2)
@@ -541,6 +566,48 @@ def body_bn_forward(be, case):
     for kk in got:
         assert got[kk] <= bars[kk], (kk, got[kk], bars[kk])
     assert got_scale <= bars["invstd"] + 1e-7 and got_shift <= bars["invstd"] + bars["mean"] + 1e-7, (got_scale, got_shift)
+    # ds_bn_stats_finalize_f32 on synthetic partial rows: the convolution cases give few rows, and nothing else reaches
+    # past the first stride of the fold's 128 row lanes.  1 / 129 / 300 rows; 66 and 65 channels: a last workgroup of
+    # the sums form (256 channels each) and of the rows form (2 channels each) that is only part full.  Reference: the
+    # same float32 rows added in float64, under the bars derived above; and the split pair, bit for bit.
+    for rows_s, cs in [(r, c) for r in (1, 129, 300) for c in (64, 66)] + [(129, 65)]:
+        rs2 = np.random.RandomState(seed_of(rows_s, cs))
+        zs = (rs2.randn(rows_s, 4, cs) * 2 + 1).astype(F32)                       # four pixels per row
+        part = np.stack([zs.sum(1), (zs * zs).sum(1)], axis=2).astype(F32)         # [rows][C][2]
+        ns = rows_s * 4
+        gam, bet = rs2.uniform(4.0, 8.0, cs).astype(F32), (8 + rs2.randn(cs)).astype(F32)
+        rms, rvs = (rs2.randn(cs) * 0.1).astype(F32), rs2.uniform(0.5, 1.5, cs).astype(F32)
+        fold = part.astype(F64).sum(0)
+        mean_s = fold[:, 0] / ns
+        var_s = np.maximum(fold[:, 1] / ns - mean_s * mean_s, 0)
+        invstd_s = 1 / np.sqrt(var_s + EPS)
+        scale_s = gam * invstd_s
+        shift_s = bet - mean_s * scale_s
+        erm_s = (1 - MOMENTUM) * rms + MOMENTUM * mean_s
+        erv_s = (1 - MOMENTUM) * rvs + MOMENTUM * var_s * (ns / (ns - 1.0))
+        part_d, gs_d, bs_d = be.put(part), be.put(gam), be.put(bet)
+        ta, tb = [be.nan(cs, F32) for _ in range(4)], [be.nan(cs, F32) for _ in range(4)]
+        ra, rb = [be.put(rms), be.put(rvs)], [be.put(rms), be.put(rvs)]
+        sums_s = be.nan(2 * cs, F64)
+        lib.call("ds_bn_stats_finalize_f32", p(part_d), rows_s, ns, p(gs_d), p(bs_d), EPS, MOMENTUM, p(ra[0]), p(ra[1]),
+                 *(p(t) for t in ta), cs, be.stream)
+        lib.call("ds_partial_sum_f64", p(part_d), rows_s, p(sums_s), cs, be.stream)
+        lib.call("ds_bn_stats_from_sums_f32", p(sums_s), ns, p(gs_d), p(bs_d), EPS, MOMENTUM, p(rb[0]), p(rb[1]),
+                 *(p(t) for t in tb), cs, be.stream)
+        mk, ik, sk, hk = (be.get(t) for t in ta)
+        got_s = {"mean": tol_err(mk, mean_s, 1e-6), "invstd": tol_err(ik, invstd_s),
+                 "running_mean": tol_err(be.get(ra[0]), erm_s, 1e-6), "running_var": tol_err(be.get(ra[1]), erv_s, 1e-6)}
+        e_scale = tol_err(sk, scale_s)
+        e_shift = float((np.abs(hk - shift_s) / (np.abs(bet) + np.abs(mean_s * scale_s) + 1e-6)).max()) if np.isfinite(hk).all() else float("inf")
+        e_fold = tol_err(be.get(sums_s).reshape(cs, 2), fold, 1e-9)
+        print(f"bn finalize, synthetic {rows_s} rows x {cs} channels: " + ", ".join(f"{kk} {got_s[kk]:.2e} (bar {bars[kk]:.2e})" for kk in got_s) +
+              f", scale {e_scale:.2e}, shift {e_shift:.2e}, float64 fold {e_fold:.2e}")
+        for kk in got_s:
+            assert got_s[kk] <= bars[kk], (rows_s, cs, kk, got_s[kk], bars[kk])
+        assert e_scale <= bars["invstd"] + 1e-7 and e_shift <= bars["invstd"] + bars["mean"] + 1e-7, (rows_s, cs, e_scale, e_shift)
+        assert e_fold <= 1e-12, (rows_s, cs, e_fold)                # float64 sums of at most 300 rows in another order
+        for a, c in zip(ta + ra, tb + rb):
+            assert be.same(a, c), f"synthetic rows {rows_s} x {cs}: split form"
     # normalise: the kernel's own tables and its own z, in float64.  A float32 evaluation rounds at most three times
     # (product, sum, residual sum), each by 2^-24 of a value no larger than `top`
     z_h = be.get(z_d).astype(F64).reshape(n, co)

@@ -28,7 +28,8 @@ def flat(x):
 # rows_cls (train_f16_cases.check_rows_class): "mid" = 128 < rows, rows % 128 != 0 -- the fold's `r += 128` loop and its
 # shuffle tree over more than two rows; "cap+0" = the 768-row cap with trailing rows that cover no pixel.  (rows x 16384
 # elements per member whatever C is: the smallest tensors that reach these paths.)
-ROWS_CASES = [(1, 1, 4129, 1, 512, "mid"), (1, 1, 3511, 7, 512, "cap+0")]
+ROWS_CASES = [(1, 1, 4129, 1, 512, "mid"), (1, 1, 3511, 7, 512, "cap+0"),
+              (3, 1, 2064, 1, 1024, "mid")]     # 129 rows x 3 members: the smallest member loop over more than one row step
 
 
 def _old(*case, extra=()):
@@ -62,6 +63,22 @@ def test_bn_stats_apply_f16(G, bm, h, w, c, rows_cls):
     erm, erv = TC.bn_running_ref(mean, var, n_pix, rm, rv, 0.1)    # members in call order: G momentum updates
     np.testing.assert_allclose(rm_, erm, rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(rv_, erv, rtol=1e-5, atol=1e-6)
+    # one formula, one fold: the data-parallel pair (partial sums -> float64 fold -> tables) and G calls with one member
+    # each on the member slices, running statistics chained in call order, give the fused call's bits
+    partial2, sums = aligned((G, rows, c, 2), np.float32, fill=np.nan), aligned((G, 2 * c + 1), np.float64, fill=np.nan)
+    tables2, tables1 = aligned((4, G, c), np.float32, fill=np.nan), aligned((4, G, c), np.float32, fill=np.nan)
+    rm2, rv2, rm1, rv1 = (to_aligned(v.copy()) for v in (rm, rv, rm, rv))
+    lib.call("ds_bn_stats_partial_f16", ptr(zz), ptr(partial2), n_pix, c, G, None)
+    lib.call("ds_partial_sum_f64_group", ptr(partial2), rows, ptr(sums), n_pix, c, G, None)
+    lib.call("ds_bn_stats_from_sums_group_f32", ptr(sums), ptr(g_), ptr(b_), 1e-5, 0.1, ptr(rm2), ptr(rv2), ptr(tables2[0]),
+             ptr(tables2[1]), ptr(tables2[2]), ptr(tables2[3]), c, G, None)
+    for m in range(G if G > 1 else 0):                      # (G = 1: the fused call itself)
+        partial1 = aligned((rows, c, 2), np.float32, fill=np.nan)
+        lib.call("ds_bn_stats_group_f16", ptr(zz[m * bm:(m + 1) * bm]), ptr(partial1), n_pix, ptr(g_), ptr(b_), 1e-5, 0.1, ptr(rm1),
+                 ptr(rv1), ptr(tables1[0][m]), ptr(tables1[1][m]), ptr(tables1[2][m]), ptr(tables1[3][m]), c, 1, None)
+    for name, other in (("split pair", (tables2, rm2, rv2)),) + ((("G calls of one member", (tables1, rm1, rv1)),) if G > 1 else ()):
+        for what, a, b in zip(("tables", "running mean", "running var"), (tables, rm_, rv_), other):
+            assert not np.isnan(b).any() and a.tobytes() == b.tobytes(), (name, what)
     variants = ((DS_EPI_CLIP, np.float16), (DS_EPI_CLIP | DS_EPI_RESIDUAL, np.float16),
                 (DS_EPI_CLIP | DS_EPI_RESIDUAL | DS_EPI_OUT_F32, np.float32), (0, np.float16))
     # (the rows cases are about the reductions: one normalise variant is enough for their large tensors)

@@ -98,6 +98,13 @@ def test_bn_stats_and_apply(eng, c, n_pix, rows_cls, dist):
     eng.lib.call("ds_partial_sum_f64_group", p(partial2), rows, p(sums), n_pix, c, G, st)
     eng.lib.call("ds_bn_stats_from_sums_group_f32", p(sums), p(g_d), p(b_d), EPS, MOMENTUM, p(rm2_d), p(rv2_d), p(tables2[0]),
                  p(tables2[1]), p(tables2[2]), p(tables2[3]), c, G, st)
+    # three G = 1 calls on the member slices, the running statistics chained in call order
+    tables1 = full((4, G, c), torch.float32)
+    rm1_d, rv1_d = dev(rm), dev(rv)
+    for m in range(G):
+        partial1 = full((rows, c, 2), torch.float32)
+        eng.lib.call("ds_bn_stats_group_f16", p(z_d[m * n_pix:(m + 1) * n_pix]), p(partial1), n_pix, p(g_d), p(b_d), EPS, MOMENTUM,
+                     p(rm1_d), p(rv1_d), p(tables1[0][m]), p(tables1[1][m]), p(tables1[2][m]), p(tables1[3][m]), c, 1, st)
     # normalise: all four flag combinations
     combos = ((DS_EPI_CLIP, torch.float16), (DS_EPI_CLIP | DS_EPI_RESIDUAL, torch.float16),
               (DS_EPI_CLIP | DS_EPI_RESIDUAL | DS_EPI_OUT_F32, torch.float32), (0, torch.float16))
@@ -130,6 +137,10 @@ def test_bn_stats_and_apply(eng, c, n_pix, rows_cls, dist):
         for k in got:
             assert got[k] <= bars[k], (name, k, got[k], bars[k])
         assert got_scale <= bars["invstd"] + 1e-7 and got_shift <= bars["invstd"] + bars["mean"] + 1e-7, (name, got_scale, got_shift)
+    # one formula, one fold: the fused call, the split pair and the member-by-member calls agree bit for bit
+    for name, other in (("split pair", (tables2, rm2_d, rv2_d)), ("three G = 1 calls", (tables1, rm1_d, rv1_d))):
+        for what, a, b in zip(("tables", "running mean", "running var"), (tables, rm_d, rv_d), other):
+            assert not torch.isnan(b).any() and torch.equal(a.view(torch.int32), b.view(torch.int32)), (name, what)
     tb = host(tables)
     for (flags, dt), y in zip(combos, ys):
         worst, top = TC.bn_apply_errors(host(y), zh, tb[2], tb[3], res.numpy() if flags & DS_EPI_RESIDUAL else None, G,
