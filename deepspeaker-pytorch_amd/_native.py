@@ -21,6 +21,8 @@ DS_CONV_HINT_ONE_QUEUE = 4096
 DS_CONV_PLAN_LATENCY = 8192
 DS_CONV_CK = 8
 DS_TAIL_SMALL_MAX_B = 4
+DS_MARGIN_AAM, DS_MARGIN_AM = 0, 1
+DS_MARGIN_SIN2_FLOOR = 1e-6      # sin^2 floor of the AAM margin's derivative (include/deepspeaker_hip.h)
 
 
 class ConvShape(Structure):
@@ -162,6 +164,14 @@ _SIGNATURES = {
     "ds_fc_ce_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "ds_cross_entropy_fwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "ds_cross_entropy_bwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "ds_row_normalize_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "ds_fc_margin_workspace_floats": (c_longlong, [c_int, c_int, c_int]),
+    "ds_fc_margin_ce_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
+                                        _P]),
+    "ds_fc_cosine_fwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "ds_margin_ce_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P]),
+    "ds_cosine_bwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
+    "ds_margin_grad_fixup_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     "ds_group_mean_f32": (c_int, [_P, _P, c_int, c_int, _P]),
     "ds_mask_rows": (c_int, [_P, _P, c_int, c_int, c_longlong, _P]),
     "ds_avgpool_time_masked_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),

@@ -12,6 +12,7 @@ There is no CPU path: tensors must live on a ROCm device, otherwise a RuntimeErr
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, Optional
 
@@ -282,6 +283,174 @@ class CrossEntropyLoss:
         return _CrossEntropyFn.apply(logits, labels, get_engine())
 
     __call__ = forward
+
+
+# ---------------------------------------------------------------------------------------------
+# angular-margin softmax head (AAM-softmax / ArcFace, AM-softmax / CosFace) on the classifier's weight
+# ---------------------------------------------------------------------------------------------
+MARGIN_KINDS = {"aam": _native.DS_MARGIN_AAM, "am": _native.DS_MARGIN_AM}
+
+
+class MarginHeadPack:
+    """The classifier's rows L2-normalised (`what`, zero rows up to a multiple of 128; `inv_w` = 1 / norm) and packed for
+    the cosine GEMM and, transposed, for the data gradient.  The bias plays no part.  Built once per version of the
+    weight (DeepSpeakerModel._margin_head)."""
+
+    def __init__(self, eng, weight):
+        n, k = weight.shape
+        if k % 128 != 0:
+            raise ValueError(f"the margin head needs an embedding size that is a multiple of 128, got {k}")
+        self.n, self.k, self.npad = n, k, _pad128(n)
+        dev = weight.device
+        st = eng._stream(weight)
+        w = weight.detach().contiguous().float()
+        self.what = torch.empty((self.npad, k), dtype=torch.float32, device=dev)
+        self.inv_w = torch.empty(self.npad, dtype=torch.float32, device=dev)
+        eng.lib.call("ds_row_normalize_f32", eng._p(w), eng._p(self.what), eng._p(self.inv_w), n, self.npad, k, st)
+        self.wp = torch.empty(self.npad * k, dtype=torch.float32, device=dev)
+        eng.lib.call("ds_pack_fc_weight_f32", eng._p(self.what), eng._p(self.wp), self.npad, k, 1, st)
+        self.wd = torch.empty(self.npad * k, dtype=torch.float32, device=dev)
+        eng.lib.call("ds_pack_fc_weight_dgrad_f32", eng._p(self.what), eng._p(self.wd), self.npad, k, 1, st)
+
+
+def _margin_normalize(eng, x):
+    m, k = x.shape
+    xhat = torch.empty((m, k), dtype=torch.float32, device=x.device)
+    inv_x = torch.empty(m, dtype=torch.float32, device=x.device)
+    eng.lib.call("ds_row_normalize_f32", eng._p(x), eng._p(xhat), eng._p(inv_x), m, m, k, eng._stream(x))
+    return xhat, inv_x
+
+
+def _margin_workspace(eng, m, k, npad, dev):
+    n_ws = eng.lib.raw("ds_fc_margin_workspace_floats")(m, k, npad)
+    if n_ws <= 0:
+        raise RuntimeError(f"ds_fc_margin_workspace_floats failed: {n_ws}")
+    return torch.empty(n_ws, dtype=torch.float32, device=dev)
+
+
+def _margin_backward(eng, pack: MarginHeadPack, xhat, inv_x, gc, r, q, need_x: bool, need_w: bool):
+    """(dL/dx, dL/dW) from gc = dL/dc [M, Np], r = rowsum(gc c), q = colsum(gc c): the plain head's two GEMMs on the
+    normalised operands, each result projected onto the tangent space of its normalisation"""
+    from ._native import ConvShape
+    from .backward import _wgrad
+    m, k = xhat.shape
+    st = eng._stream(xhat)
+    gx = gw = None
+    if need_x:
+        ws = torch.empty(eng.lib.raw("ds_fc_workspace_floats")(m, pack.npad, k), dtype=torch.float32, device=xhat.device)
+        a = torch.empty((m, k), dtype=torch.float32, device=xhat.device)
+        eng.lib.call("ds_fc_l2norm_fwd_f32", eng._p(gc), eng._p(pack.wd), None, eng._p(ws), eng._p(a), None, m, pack.npad, k,
+                     1.0, 0.0, st)                                  # A = gc W^
+        gx = torch.empty_like(a)
+        eng.lib.call("ds_margin_grad_fixup_f32", eng._p(a), eng._p(xhat), eng._p(r), eng._p(inv_x), eng._p(gx), m, k, st)
+    if need_w:
+        shp = ConvShape(1, m, 1, k, pack.npad, 1, 1)                # Bm = gc^T x^: a 1x1 "convolution" over the M rows
+        bm = _wgrad(eng, shp, xhat, gc, (pack.npad, k))
+        gw = torch.empty((pack.n, k), dtype=torch.float32, device=xhat.device)
+        eng.lib.call("ds_margin_grad_fixup_f32", eng._p(bm), eng._p(pack.what), eng._p(q), eng._p(pack.inv_w), eng._p(gw),
+                     pack.n, k, st)
+    return gx, gw
+
+
+class _MarginHeadFn(torch.autograd.Function):
+    """loss = mean CE(scale * margin(cos(x, W)), labels) with the clamp, the margin, the row maximum, the log-sum-exp and
+    the per-row loss taken in the cosine GEMM's reduction epilogue (ds_fc_margin_ce_fwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, labels, eng, pack, scale, margin, kind):
+        x = x.contiguous().float()
+        m, k = x.shape
+        dev = x.device
+        labels = labels.to(torch.int64).contiguous()
+        xhat, inv_x = _margin_normalize(eng, x)
+        ws = _margin_workspace(eng, m, k, pack.npad, dev)
+        c = torch.empty((m, pack.npad), dtype=torch.float32, device=dev)
+        row_loss, lse = torch.empty(m, dtype=torch.float32, device=dev), torch.empty(m, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        eng.lib.call("ds_fc_margin_ce_fwd_f32", eng._p(xhat), eng._p(pack.wp), eng._p(ws), eng._p(c), eng._p(labels),
+                     eng._p(row_loss), eng._p(lse), eng._p(loss), m, k, pack.npad, pack.n, scale, margin, kind,
+                     eng._stream(x))
+        ctx.save_for_backward(xhat, inv_x, c, labels, lse)
+        ctx.eng, ctx.pack, ctx.rule = eng, pack, (scale, margin, kind)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        xhat, inv_x, c, labels, lse = ctx.saved_tensors
+        eng, pack = ctx.eng, ctx.pack
+        m, dev = xhat.shape[0], xhat.device
+        gc = torch.empty((m, pack.npad), dtype=torch.float32, device=dev)
+        r = torch.empty(m, dtype=torch.float32, device=dev)
+        q = torch.empty(pack.npad, dtype=torch.float32, device=dev)
+        gl = gl.reshape(1).contiguous().float()
+        eng.lib.call("ds_margin_ce_bwd_f32", eng._p(c), eng._p(labels), eng._p(lse), eng._p(gl), eng._p(gc), eng._p(r),
+                     eng._p(q), m, pack.npad, pack.n, *ctx.rule, eng._stream(xhat))
+        gx, gw = _margin_backward(eng, pack, xhat, inv_x, gc, r, q, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gx, gw, None, None, None, None, None, None
+
+
+class _CosineHeadFn(torch.autograd.Function):
+    """scale * cos(x, W) [M, n_cls]: the margin head's GEMM and clamp without margin or loss; the backward pass is the
+    margin head's with dphi/dc = 1 everywhere."""
+
+    @staticmethod
+    def forward(ctx, x, weight, eng, pack, scale):
+        x = x.contiguous().float()
+        m, k = x.shape
+        dev = x.device
+        xhat, inv_x = _margin_normalize(eng, x)
+        ws = _margin_workspace(eng, m, k, pack.npad, dev)
+        c = torch.empty((m, pack.npad), dtype=torch.float32, device=dev)
+        out = torch.empty((m, pack.n), dtype=torch.float32, device=dev)
+        eng.lib.call("ds_fc_cosine_fwd_f32", eng._p(xhat), eng._p(pack.wp), eng._p(ws), eng._p(c), eng._p(out), m, k,
+                     pack.npad, pack.n, scale, eng._stream(x))
+        ctx.save_for_backward(xhat, inv_x, c)
+        ctx.eng, ctx.pack, ctx.scale = eng, pack, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xhat, inv_x, c = ctx.saved_tensors
+        eng, pack = ctx.eng, ctx.pack
+        m, dev = xhat.shape[0], xhat.device
+        g = g.contiguous().float()
+        gc = torch.empty((m, pack.npad), dtype=torch.float32, device=dev)
+        r = torch.empty(m, dtype=torch.float32, device=dev)
+        q = torch.empty(pack.npad, dtype=torch.float32, device=dev)
+        eng.lib.call("ds_cosine_bwd_f32", eng._p(c), eng._p(g), eng._p(gc), eng._p(r), eng._p(q), m, pack.npad, pack.n,
+                     ctx.scale, eng._stream(xhat))
+        gx, gw = _margin_backward(eng, pack, xhat, inv_x, gc, r, q, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gx, gw, None, None, None
+
+
+def _check_margin_args(what: str, embeddings, k: int, scale, margin=0.0, kind="am", labels=None):
+    """host-side checks of a margin-head call: types and ranges of the scalars, dtype and shape of the tensors (label
+    VALUES are the caller's promise -- checking them would read the device back)"""
+    for name, v in (("scale", scale), ("margin", margin)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError(f"{what}: {name} must be a Python number, got {type(v).__name__}")
+    if not isinstance(kind, str) or kind not in MARGIN_KINDS:
+        raise ValueError(f"{what}: kind must be one of {sorted(MARGIN_KINDS)}, got {kind!r}")
+    # the kernels take both as float32: the ranges must hold for the values they will see (1e39 is inf there, 1e-50 is 0,
+    # and the float32 nearest pi/2 lies above it)
+    try:
+        scale32, margin32 = ctypes.c_float(scale).value, ctypes.c_float(margin).value
+    except OverflowError:
+        scale32, margin32 = math.inf, math.inf
+    if not (scale32 > 0 and math.isfinite(scale32)):
+        raise ValueError(f"{what}: scale must be positive and finite in float32, got {scale}")
+    if not 0 <= margin32 < math.pi / 2:
+        raise ValueError(f"{what}: margin must lie in [0, pi/2) in float32, got {margin}")
+    if embeddings.dim() != 2 or embeddings.shape[1] != k or not embeddings.is_floating_point():
+        raise ValueError(f"{what}: embeddings must be a floating-point [M, {k}] tensor, got {embeddings.dtype} "
+                         f"{tuple(embeddings.shape)}")
+    if embeddings.shape[0] < 1:
+        raise ValueError(f"{what}: no rows")
+    if labels is not None:
+        if labels.dtype in (torch.bool,) or labels.is_floating_point() or labels.is_complex():
+            raise TypeError(f"{what}: labels must be an integer tensor, got {labels.dtype}")
+        if tuple(labels.shape) != (embeddings.shape[0],):
+            raise ValueError(f"{what}: labels must have shape ({embeddings.shape[0]},), got {tuple(labels.shape)}")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -930,6 +1099,43 @@ class DeepSpeakerModel(nn.Module):
         _require_cuda(embeddings, "DeepSpeakerModel.classifier_loss")
         return _HeadCrossEntropyFn.apply(embeddings, self.model.classifier.weight, self.model.classifier.bias, labels,
                                          get_engine(), self._head())
+
+    def _margin_head(self) -> MarginHeadPack:
+        w = self.model.classifier.weight
+        key = (w.data_ptr(), w._version)
+        if getattr(self, "_margin_head_key", None) != key:
+            self._margin_head_cache, self._margin_head_key = MarginHeadPack(get_engine(), w), key
+        return self._margin_head_cache
+
+    def margin_loss(self, embeddings, labels, margin: float = 0.2, scale: float = 30.0, kind: str = "aam"):
+        """Angular-margin softmax loss on the classifier's weight (its bias is ignored and receives no gradient):
+        kind "aam" is AAM-softmax / ArcFace, cos(theta + margin) at the label with ArcFace's monotone fallback past
+        theta = pi - margin; "am" is AM-softmax / CosFace, cos(theta) - margin.  The mean over the rows of
+        CrossEntropy(scale * cosines, labels), in f32 whatever `train_precision` is, as one fused chain: normalise,
+        cosine GEMM with clamp + margin + log-sum-exp + row loss in its reduction epilogue.  Gradients flow to
+        `classifier.weight` and into `embeddings`.  `margin` (0 <= margin < pi/2) and `scale` (> 0) are per-call
+        Python numbers, so a schedule can warm the margin up.  `labels`: an integer tensor [M] with values in
+        [0, num_classes) -- the values are not checked (that would read the device back).  Forward and backward
+        capture into a `torch.cuda.graph` as `train_graph.GraphedTripletStep` captures its step
+        (`capture_error_mode="thread_local"`: autograd's worker thread enqueues the backward kernels).  The
+        normalised and packed copies of the weight are built HERE, on the host's view of the weight's version: a graph
+        captured after a warm-up call holds the copies of the capture and does not rebuild them, so replaying it after
+        the weight has changed computes with the old weight -- re-capture, or keep optimizer steps out of such a graph."""
+        _require_cuda(embeddings, "DeepSpeakerModel.margin_loss")
+        _require_cuda(labels, "DeepSpeakerModel.margin_loss")
+        _check_margin_args("DeepSpeakerModel.margin_loss", embeddings, self.model.classifier.weight.shape[1], scale, margin,
+                           kind, labels)
+        return _MarginHeadFn.apply(embeddings, self.model.classifier.weight, labels, get_engine(), self._margin_head(),
+                                   float(scale), float(margin), MARGIN_KINDS[kind])
+
+    def classify_cosine(self, embeddings, scale: float = 1.0):
+        """[M, num_classes] = scale * cos(embeddings, classifier rows), clamped to [-1, 1] before the scale: the margin
+        head's logits without the margin, for monitoring accuracy during `margin_loss` pre-training.  Differentiable
+        (to `classifier.weight` and `embeddings`) through the margin head's own backward kernels."""
+        _require_cuda(embeddings, "DeepSpeakerModel.classify_cosine")
+        _check_margin_args("DeepSpeakerModel.classify_cosine", embeddings, self.model.classifier.weight.shape[1], scale)
+        return _CosineHeadFn.apply(embeddings, self.model.classifier.weight, get_engine(), self._margin_head(),
+                                   float(scale))
 
     def forward_classifier(self, x):
         """reference model.py:220-223: logits = classifier(embedding x10), on the f32 matrix cores."""

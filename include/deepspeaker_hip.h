@@ -512,6 +512,49 @@ int ds_cross_entropy_bwd_f32(const float *logits, const long long *labels, const
                              const float *grad_loss, float *dlogits, int M, int n_cls, int ld, int ld_out,
                              void *stream);
 
+/* ---- angular-margin softmax head (margin_head.hip): AAM-softmax / ArcFace and AM-softmax / CosFace on the
+ *      classifier's weight, f32.  With x^, w^ the L2-normalised rows (an all-zero row stays zero):
+ *        c[i,j] = clamp(x^_i . w^_j, -1, 1);   z[i,j] = scale c[i,j] for j != y_i,   z[i,y_i] = scale phi(c[i,y_i])
+ *        DS_MARGIN_AM:   phi = c - m                                                      dphi/dc = 1
+ *        DS_MARGIN_AAM:  phi = c cos m - sn sin m,  sn = sqrt(max(1 - c^2, DS_MARGIN_SIN2_FLOOR))   where c > -cos m
+ *                                                                                         dphi/dc = cos m + c sin m / sn
+ *                        phi = c - m sin m  otherwise (ArcFace's monotone fallback)        dphi/dc = 1
+ *        loss = mean_i (logsumexp_{j < n_cls} z[i,j] - z[i,y_i])
+ *      scale > 0, 0 <= margin < pi/2 (else DS_ERR_BAD_SHAPE); another kind is DS_ERR_UNSUPPORTED.  Labels in [0, n_cls)
+ *      are the caller's promise: no entry point reads device memory back, and none indexes memory by a label.
+ * ds_row_normalize_f32: x [R, K] -> xhat [R_out, K] = rows / norm and inv [R_out] = 1 / norm (both 0 for an all-zero
+ *   row); rows R .. R_out-1 are written as zeros (class rows padded to a multiple of 128 for the two weight packers).
+ * ds_fc_margin_ce_fwd_f32: xhat [M, K]; w_packed = ds_pack_fc_weight_f32(what [N, K], N, K, 1), N = n_cls padded to a
+ *   multiple of 128; K % 32 == 0.  The split-K GEMM's reduction epilogue folds the K-slices, clamps, stores c [M, N]
+ *   (pad columns 0), applies the margin and takes lse [M] and row_loss [M] over the n_cls real columns in one pass;
+ *   loss = their mean.  workspace: ds_fc_margin_workspace_floats(M, K, N) floats, 16-byte aligned.
+ * ds_fc_cosine_fwd_f32: the same GEMM and c; cos_out [M, n_cls] = scale c, no margin and no loss.
+ * ds_margin_ce_bwd_f32: gc [M, N] = scale (grad_loss[0] / M) (exp(z - lse) - [j == y_i]), the label column times
+ *   dphi/dc, pad columns 0 (the clamp passes gradient everywhere); r [M] = sum_j gc c; q [N] = sum_i gc c, summed in one
+ *   fixed order without atomics.  ds_cosine_bwd_f32: the same outputs for gc = scale grad_out [M, n_cls].
+ * ds_margin_grad_fixup_f32: out [R, K] = inv[row] (g - coef[row] u), rows of K % 4 == 0 floats: with A = gc what
+ *   (ds_fc_l2norm_fwd_f32 on ds_pack_fc_weight_dgrad_f32's layout) and Bm = gc^T xhat (ds_conv_wgrad_f32, a 1x1
+ *   convolution over the M rows),  dL/dx = fixup(A, xhat, r, inv_x)  and  dL/dW = fixup(Bm, what, q, inv_w).
+ * Every sum has one order that depends on its row (q: its column and M) alone: two calls agree bit for bit, and a
+ * row's c, loss and gradient do not depend on the other rows of the batch. ---- */
+#define DS_MARGIN_AAM 0
+#define DS_MARGIN_AM  1
+#define DS_MARGIN_SIN2_FLOOR 1e-6f
+int ds_row_normalize_f32(const float *x, float *xhat, float *inv, int R, int R_out, int K, void *stream);
+long long ds_fc_margin_workspace_floats(int M, int K, int N);
+int ds_fc_margin_ce_fwd_f32(const float *xhat, const float *w_packed, float *workspace, float *c,
+                            const long long *labels, float *row_loss, float *lse, float *loss, int M, int K, int N,
+                            int n_cls, float scale, float margin, int kind, void *stream);
+int ds_fc_cosine_fwd_f32(const float *xhat, const float *w_packed, float *workspace, float *c, float *cos_out, int M,
+                         int K, int N, int n_cls, float scale, void *stream);
+int ds_margin_ce_bwd_f32(const float *c, const long long *labels, const float *lse, const float *grad_loss, float *gc,
+                         float *r, float *q, int M, int N, int n_cls, float scale, float margin, int kind,
+                         void *stream);
+int ds_cosine_bwd_f32(const float *c, const float *grad_out, float *gc, float *r, float *q, int M, int N, int n_cls,
+                      float scale, void *stream);
+int ds_margin_grad_fixup_f32(const float *g, const float *u, const float *coef, const float *inv, float *out, int R,
+                             int K, void *stream);
+
 /* ---- variable-length batches (BASELINE configs[4]; the temporal mean pool of model.py:207 accepts any T) --------
  * Utterances of different lengths share one zero-padded batch [B,1,Tmax,64].  ds_mask_rows re-zeroes, after every
  * layer, the rows past each utterance's own extent (lens[b] rows of the [H][row_bytes] slab of image b are kept):
