@@ -40,8 +40,8 @@ class _FusedBase(torch.optim.Optimizer):
     def enable_device_step(self):
         """From now on the step count that enters the update lives on the device (initialised from the host-side counts;
         all parameters must share one count).  Host-side `state[p]["step"]` keeps advancing in eager steps; after graph
-        replays `sync_host_steps()` brings it up to date (one host synchronisation).  A step skipped by the overflow flag
-        does not count (as with torch.amp.GradScaler, which does not call step() at all)."""
+        replays `sync_host_steps()` brings it up to date (one host synchronisation; `state_dict()` does it).  A step skipped
+        by the overflow flag does not count (as with torch.amp.GradScaler, which does not call step() at all)."""
         self._dev_step_on = True                # (the counter itself is created at the first step, where the parameters are)
         return self
 
@@ -49,17 +49,34 @@ class _FusedBase(torch.optim.Optimizer):
         """the counter, on the device the parameters are on NOW (created at first use; follows a model that was moved)"""
         dev = params[0].device
         if self._dev_step is None:
-            allp = [p for g in self.param_groups for p in g["params"]]
-            counts = {float(self.state[p]["step"]) for p in allp if "step" in self.state.get(p, {})}
+            counts = self._host_counts()
             if len(counts) > 1:
                 raise RuntimeError(f"device-side step count needs one count for all parameters, found {sorted(counts)}")
-            start = int(counts.pop()) if counts else 0
-            if start == 0 and any("momentum_buffer" in self.state.get(p, {}) for p in allp):
-                start = 1                       # SGD keeps no step count: buffers that exist are past their first step
-            self._dev_step = torch.full((1,), start, dtype=torch.int32, device=dev)
+            self._dev_step = torch.full((1,), self._start_count(counts), dtype=torch.int32, device=dev)
         elif self._dev_step.device != dev:
             self._dev_step = self._dev_step.to(dev)
         return self._dev_step
+
+    def _host_counts(self):
+        """the distinct host-side step counts of the parameters that have one"""
+        return {float(self.state[p]["step"]) for g in self.param_groups for p in g["params"] if "step" in self.state.get(p, {})}
+
+    def _start_count(self, counts):
+        """what the device counter holds for host-side state with the one count in `counts` (or none)"""
+        start = int(next(iter(counts))) if counts else 0
+        if start == 0 and any("momentum_buffer" in self.state.get(p, {}) for g in self.param_groups for p in g["params"]):
+            start = 1                           # SGD keeps no step count: buffers that exist are past their first step
+        return start
+
+    def load_state_dict(self, state_dict):
+        """torch's, and a device counter that already exists takes the loaded count -- by the rule it is created with, and
+        IN PLACE: a captured step (train_graph.GraphedTripletStep) replays with that tensor's address.  A checkpoint whose
+        parameters carry different counts leaves it alone: such steps use the host-side counts (_use_dev_step)."""
+        super().load_state_dict(state_dict)
+        if self._dev_step is not None:
+            counts = self._host_counts()
+            if len(counts) <= 1:
+                self._dev_step.fill_(self._start_count(counts))
 
     def sync_host_steps(self):
         if self._dev_step is None:
@@ -216,6 +233,12 @@ class _FusedBase(torch.optim.Optimizer):
                 eng._p(c["ct"]), eng._p(c["ci"]), c["n_chunks"])
 
     def state_dict(self):
+        """torch's, with the step counts the device holds: in device-step mode a step skipped by the overflow flag (or a
+        graph replay) moves the device counter and the host-side `state[p]["step"]` apart, and a checkpoint must resume
+        from the count the updates were made with -- sync_host_steps() first, ONE host synchronisation per checkpoint.
+        (Not while the parameters carry different counts: those steps use the host-side counts, _use_dev_step.)"""
+        if self._dev_step is not None and len(self._host_counts()) <= 1:
+            self.sync_host_steps()
         sd = super().state_dict()
         for g in sd["param_groups"]:
             g.pop("_ds_cache", None)
