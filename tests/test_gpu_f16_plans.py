@@ -8,7 +8,7 @@ Template instantiations these cases reach, read off the recorded plans (B, Cin, 
   k5db    the NO_PERSIST run of every 5x5 case, (1, 64, 128, 21, 64) by default (14 items)
   k5c16   the CHUNK16 | NO_PERSIST run of every 5x5 case
   k3sb / k5sb   not here: a plan is single-buffered only under the SINGLE_BUFFER hint at these sizes, which
-          test_gpu_bench_size.py::test_conv_f16_kernel runs
+          test_gpu_bench_size.py::test_conv_f16_kernel and test_gpu_f16_kernels.py (every configuration) run
   pk3     LIN at 16 items: (2, 64, 64, 11, 32), (3 / 96, 64, 64, 27, 32) (12 items); LIN at 8: (3 / 9, 32, 128, 20, 8),
           (2, 32, 128, 100, 4); without LIN: (5, 96, 128, 10, 4), (11, 64, 128, 10, 4), (1, 64, 64, 3, 5)
   pk5     without LIN: (3 / 7, 32, 256, 9, 8); LIN at 16 items: (3, 64, 128, 43, 16) (11 items)
@@ -16,9 +16,10 @@ Template instantiations these cases reach, read off the recorded plans (B, Cin, 
   cfg 7   (7, 64, 256, 10, 4), (8, 32, 512, 10, 4), (40, 64, 256, 10, 4) -- and cfg 4 of the same layers under NO_WIDE
   block   both widths: <2, 1, 12> at (3, 11, 32, 64), <1, 2, 6> at (3, 11, 16, 128), and the MASKED form of each
 All of these plan the two-wave configurations 3, 4 and 7.  The four-wave ones (1, 2, 5) are what the planner picks for the
-network's layers at bench-size batches (rows of the golden file at batch 768): the end-to-end forwards of
-test_gpu_bench_size.py and the batch-768 layers of test_gpu_parity.py run them; configurations 0 and 6 win no recorded shape
-and are reached only when forced (tools/f16_cfg_ab.py)."""
+network's layers at bench-size batches (rows of the golden file at batch 768), and configurations 0 and 6 win no recorded
+shape (tools/f16_cfg_ab.py forces them): test_gpu_f16_kernels.py launches every kernel under each of 0 .. 6 forced in turn --
+persistent and one tile per workgroup, single-buffered, 16-channel chunks, plane-major input and output, workgroups that walk
+several tiles, split-K up to 8 ways, the block kernel's XCD-dealt order -- against float64 and bit for bit among them."""
 import ctypes
 
 import pytest
