@@ -227,14 +227,30 @@ DS_ERR_NO_WORKSPACE = -5
 # entry points that launch persistent kernels (tiles drawn from device-side counters in the caller's scheduler workspace)
 _PERSISTENT = ("ds_conv_fwd_f16", "ds_conv_fwd_f16_splitk", "ds_conv_block_f16", "ds_conv_block_f16_masked")
 
+# Every scheduler workspace ever handed to a library, by (real path of the shared library, device): the pool that keeps
+# their raw pointers is a process-wide static INSIDE the shared library (csrc/runtime.hip), shared by every NativeLib on
+# that path and never emptied -- so the tensors live here, for the life of the process, not on the instance that happened
+# to allocate them (tests and tools build second instances; one that was garbage-collected freed memory the
+# library went on handing out as tile counters).
+_SCHED_WORKSPACES = {}
+
+
+def sched_workspaces(path=None):
+    """The registry above (a copy), or the buffers of one library path over all its devices."""
+    if path is None:
+        return {k: list(v) for k, v in _SCHED_WORKSPACES.items()}
+    real = os.path.realpath(path)
+    return [b for (p, _), bufs in _SCHED_WORKSPACES.items() if p == real for b in bufs]
+
 
 class NativeLib:
     """A loaded copy of the C ABI with argument types declared.
 
     The library owns no device memory: the persistent kernels' tile-scheduling slots live in zeroed buffers this wrapper
     allocates through torch's allocator (`add_sched_workspace`: one int32 tensor of ds_sched_workspace_bytes() per hand-
-    over, kept alive for the life of the process) -- eagerly when a model is moved to a device
-    (DeepSpeakerModel._apply), and on demand when a persistent launch reports DS_ERR_NO_WORKSPACE."""
+    over, kept alive for the life of the process in the module's `_SCHED_WORKSPACES`, whatever becomes of this
+    instance) -- eagerly when a model is moved to a device (DeepSpeakerModel._apply), before a stream capture
+    (`reserve_sched_slots`), and on demand when a persistent launch reports DS_ERR_NO_WORKSPACE."""
 
     def __init__(self, path: str, host_memory: bool = False):
         # host_memory: tests only -- the library at `path` is the host emulator (tests/emul), its "device" memory is the host's
@@ -251,13 +267,14 @@ class NativeLib:
             fn.restype = res
             fn.argtypes = args
             setattr(self, "_" + name, fn)
-        self._sched_workspaces = []
+        self.persistent_launches = 0            # calls of the _PERSISTENT entry points so far (reserve_sched_slots)
         for name in _PERSISTENT:
             if name in _SIGNATURES:
                 setattr(self, "_" + name, self._with_workspace(name, getattr(self, "_" + name)))
 
     def _with_workspace(self, name, fn):
         def call(*args):
+            self.persistent_launches += 1
             rc = fn(*args)
             if rc == DS_ERR_NO_WORKSPACE:       # first persistent launch on this device (or every slot taken by graphs)
                 self.add_sched_workspace()
@@ -276,6 +293,8 @@ class NativeLib:
             if not torch.cuda.is_available():
                 raise DeepSpeakerHipError("no ROCm device: deepspeaker-pytorch_amd computes only on an MI355X")
             dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            if dev.index is None:               # "cuda": the current device, under its canonical name (the registry's key)
+                dev = torch.device("cuda", torch.cuda.current_device())
             if torch.cuda.is_current_stream_capturing():
                 raise DeepSpeakerHipError("the persistent kernels' scheduler workspace on " + str(dev) + " is missing or used "
                                           "up and cannot be allocated inside a stream capture: call "
@@ -291,7 +310,9 @@ class NativeLib:
             rc = self._ds_sched_set_workspace(ctypes.c_void_p(buf.data_ptr()), n)
         if rc != 0:
             raise DeepSpeakerHipError(f"ds_sched_set_workspace failed: {rc} ({self.error_string(rc)})")
-        self._sched_workspaces.append(buf)
+        key = (os.path.realpath(self.path), "cpu" if self.host_memory else str(dev))
+        _SCHED_WORKSPACES.setdefault(key, []).append(buf)
+        return buf
 
     def ensure_sched_workspace(self, device, min_free: int = 64):
         """At least `min_free` unassigned slots on `device` (called when a model is moved there: a capture whose first
@@ -302,6 +323,25 @@ class NativeLib:
             return
         with torch.cuda.device(dev):
             if int(self._ds_sched_free_slots()) < min_free:
+                self.add_sched_workspace(dev)
+
+    def reserve_sched_slots(self, device, launches: int, margin: int = 16):
+        """Before a stream capture, OUTSIDE it: at least `launches` + `margin` unassigned slots on `device`.  Every
+        persistent launch that is captured keeps one slot for good (csrc/runtime.hip), and a pool that runs out inside
+        the capture cannot be topped up there (`add_sched_workspace` refuses).  `launches`: what one warm-up run of the
+        code about to be captured counted in `persistent_launches`.  Slots are never handed back -- there is no ABI for
+        it: a graph that is rebuilt (new learning rate, new batch shape) keeps the slots of the old one, 64 bytes each,
+        a few KB per rebuild, and a new 64 KB buffer every dozen or so rebuilds of a training step."""
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda" or self.host_memory:
+            return
+        per_buffer = int(self._ds_sched_workspace_bytes()) // 64
+        need = int(launches) + int(margin)
+        with torch.cuda.device(dev):
+            for _ in range(need // per_buffer + 2):
+                if int(self._ds_sched_free_slots()) >= need:
+                    break
                 self.add_sched_workspace(dev)
 
     def error_string(self, code: int) -> str:

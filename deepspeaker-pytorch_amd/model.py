@@ -619,11 +619,18 @@ class GraphedEmbedder:
         cur = torch.cuda.current_stream(example.device)
         side = torch.cuda.Stream(device=example.device)
         side.wait_stream(cur)
+        lib = get_engine().lib
+        launched = lib.persistent_launches
         with torch.no_grad(), torch.cuda.stream(side):     # warm-up off the capture: launch plans, LDS opt-ins
             for _ in range(3):
                 model(self.static_x)
         cur.wait_stream(side)
         torch.cuda.synchronize(example.device)
+        # every captured persistent launch keeps a scheduler slot for good, and the pool cannot be topped up inside the
+        # capture: secure what ONE forward launches now (a third of the warm-up's count, rounded up; where the warm-up
+        # also ran the precision guard's first check, that is an upper bound).  Slots are not handed back when this
+        # object goes: a few KB per re-capture.
+        lib.reserve_sched_slots(example.device, -(-(lib.persistent_launches - launched) // 3))
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
             self.static_e = model(self.static_x)
@@ -741,7 +748,9 @@ class DeepSpeakerModel(nn.Module):
         canonical step is three `model(x)` calls, i.e. three backward passes per `loss.backward()`, and so is gradient
         accumulation -- and the fused optimizers of `optim.create_optimizer(model, ...)` CONSUME it: they read it on the
         device, skip the update while it is set (no host synchronisation), then latch it into `grad_overflow` and clear
-        it (`_consume_overflow`).  `loss_scale` itself is static unless the training loop calls `update_loss_scale()`."""
+        it (`_consume_overflow`).  A loop stepped by anything else -- torch.optim.*, a fused optimizer built by hand
+        without `skip_flag` -- must call `consume_overflow()` (or `update_loss_scale()`, which does) once per step: there
+        the flag has no other consumer.  `loss_scale` itself is static unless the loop calls `update_loss_scale()`."""
         dev = torch.device(device if device is not None else next(self.parameters()).device)
         st = self.__dict__.get("_overflow_state")
         if st is None or st.device != dev:
@@ -761,20 +770,50 @@ class DeepSpeakerModel(nn.Module):
             st[1:2].copy_(st[0:1])
             st[0:1].zero_()
 
+    def consume_overflow(self) -> bool:
+        """What the fused optimizers do on the device, for the host: did a backward pass since the flag was last consumed
+        overflow?  The pending flag is latched for `grad_overflow` / `update_loss_scale` and cleared (`_consume_overflow`),
+        and its value returned: one host synchronisation.  This is what a loop WITHOUT a consuming optimizer -- torch.optim.*, as the
+        reference loop builds, or a fused optimizer constructed by hand without `skip_flag` -- must call once per
+        optimizer step, after the step's last backward pass: nothing else ever clears the flag there, and nothing skips
+        the update either:
+
+            loss.backward()                         # (or several passes: gradient accumulation)
+            if not model.consume_overflow():
+                optimizer.step()                    # inf / NaN gradients never reach the parameters
+            model.update_loss_scale()               # optional; backs off on the verdict just consumed
+
+        `update_loss_scale()` consumes by itself, so a loop that calls it every step (and can live with the update of an
+        overflowed step) needs nothing else.  The optimizers of `optim.create_optimizer` need neither: they consume the
+        flag on the device inside `step()` (read what they latched with `grad_overflow`).  The verdict stays readable
+        through `grad_overflow` until the flag is consumed again -- here, by a fused step, or by `update_loss_scale()`:
+        the device pair [pending, latched] is the only state."""
+        st = self.__dict__.get("_overflow_state")
+        if st is None:
+            return False
+        bad = bool(st[0:1].item())
+        self._consume_overflow()
+        return bad
+
     @property
     def grad_overflow(self) -> bool:
         """Did the backward passes of the last optimizer step (or the passes since it) overflow?  (Reads the flags: a
-        host synchronisation.)"""
+        host synchronisation; clears nothing -- see `consume_overflow`.)"""
         st = self.__dict__.get("_overflow_state")
         return bool(st.max().item()) if st is not None else False
 
     def update_loss_scale(self, backoff: float = 0.5, growth: float = 2.0, growth_interval: int = 2000,
                           max_scale: float = 65536.0) -> bool:
-        """Dynamic loss scaling for loops that want it (torch.amp.GradScaler.update's rule): call after optimizer.step().
-        Overflow in the last pass -> loss_scale *= backoff (that step was skipped on the device); `growth_interval` clean
-        passes in a row -> loss_scale *= growth.  One host synchronisation per call; returns whether the step overflowed."""
+        """Dynamic loss scaling for loops that want it (torch.amp.GradScaler.update's rule): call ONCE per optimizer
+        step, after optimizer.step() (or after the `consume_overflow()` that stood in for it).
+        Overflow in the last step -> loss_scale *= backoff, not below 1.0 (with `create_optimizer`'s optimizers that step
+        was skipped on the device); `growth_interval` clean steps in a row -> loss_scale *= growth, not above `max_scale`.
+        The call reads BOTH flags -- pending (nobody consumed this step's passes) or latched (the fused step, or the
+        loop's `consume_overflow()`, did) -- and clears both: with any optimizer -- fused, hand-built or torch.optim.* --
+        the next clean step reads clean.  One host synchronisation per call; returns whether the step overflowed."""
         bad = self.grad_overflow
         if bad:
+            self.__dict__["_overflow_state"].zero_()
             self.loss_scale = max(1.0, self.loss_scale * backoff)
             self._clean_steps = 0
         else:

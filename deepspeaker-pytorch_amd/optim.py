@@ -27,6 +27,9 @@ class _FusedBase(torch.optim.Optimizer):
     # (`skip_source`, a weak reference): the flag is then resolved at every step() on the device the parameters are on
     # NOW (a model moved with .cuda() after the optimizer was built gets a flag there, never a stale or host pointer), and
     # the model latches the consumed value for `grad_overflow` / `update_loss_scale()`.
+    # An optimizer WITHOUT either (built by hand, no `skip_flag`) neither skips nor consumes: its loop must call
+    # `model.consume_overflow()` after the step's last backward pass and step only when that returns False -- as a loop
+    # around torch.optim.* must (DeepSpeakerModel.consume_overflow).
     # The host-side step counters (Adagrad's decayed lr, Adam's bias correction) still advance on a skipped step -- unlike
     # torch.amp.GradScaler, which does not call optimizer.step() at all: undoing them would need the flag on the host.
     _skip_tensor = None
@@ -352,7 +355,8 @@ class FusedAdam(_FusedBase):
 def create_optimizer(model, new_lr, optimizer="adagrad", lr_decay=1e-4, wd=0.0):
     """train_triplet.py:369-383 with the fused implementations (same hyper-parameters).  A model whose training step is the
     loss-scaled fp16 one (train_precision="f16") hands the optimizer its gradient-overflow flag: a step whose scaled
-    gradients left fp16's range updates nothing."""
+    gradients left fp16's range updates nothing.  (Any other optimizer on such a model -- torch.optim.*, a fused one built
+    by hand -- has no such wiring: its loop calls `model.consume_overflow()` and steps only when that returns False.)"""
     if optimizer == "sgd":
         opt = FusedSGD(model.parameters(), lr=new_lr, momentum=0.9, dampening=0.9, weight_decay=wd)
     elif optimizer == "adam":

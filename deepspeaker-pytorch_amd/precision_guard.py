@@ -13,8 +13,9 @@ escalates:
     f32-class path (split-operand bf16, 1e-5 from the reference), reduces max |e16 - e32| / max |e32| on the device
     (`ds_max_abs_diff_f32`; a non-finite difference reads as an infinite error) and reads it back -- one host
     synchronisation per weight generation.  The rate limit (`min_gap` forwards between synchronous checks) applies
-    only while the weights change on EVERY forward (an evaluation interleaved with optimizer steps);
-    `load_state_dict` and a train -> eval transition always re-arm the check;
+    while the weights KEEP changing -- a forward that finds new weights (or weights not measured yet) is rate-limited
+    when an earlier one of the last `min_gap` forwards found new weights too, however many forwards share a
+    generation; `load_state_dict` and a train -> eval transition always re-arm the check;
   * estimate of the whole batch's error = `sample_factor` x the sample's (a maximum over 32 x 512 values against one
     over 768 x 512 of the same distribution: 4.4 against 5.1 standard deviations);
   * estimate > `threshold` (0.7e-3: the contract with 30 % to spare) => every eval forward of this model runs the
@@ -60,7 +61,7 @@ class F16Guard:
         self.pending = None             # an asynchronous re-check in flight
         self._below = 0                 # consecutive measurements below the de-escalation bar while escalated
         self._seen = None               # weight generation the previous forward saw
-        self._changed_last = False      # ... and whether THAT forward had seen a change too (weights changing every call)
+        self._last_change = -(1 << 30)  # `calls` at the most recent forward that saw a NEW generation
         self._samples = 0               # checks of either kind so far: moves the sample's first row
 
     def invalidate(self):
@@ -68,7 +69,7 @@ class F16Guard:
         whatever the rate limit says (a warm-up forward followed by a checkpoint load, or a sweep over
         checkpoints with fewer than `min_gap` forwards each, was never measured)."""
         self.last_check = -(1 << 30)
-        self._changed_last = False
+        self._last_change = -(1 << 30)
 
     def _sample(self, x: torch.Tensor, lengths=None):
         """`rows` utterances spread over the whole batch (not its head: a batch is anchors | positives | negatives, or
@@ -178,11 +179,16 @@ class F16Guard:
         model._folded()
         key = (model._pack_key, model._fold_key)
         changed = self._seen is not None and key != self._seen
-        # rate-limited only while the weights change on every forward (this one and the one before it both saw new
-        # weights): a single change -- a checkpoint loaded after a warm-up forward -- is measured at once
-        every_call = changed and self._changed_last
-        self._seen, self._changed_last = key, changed
-        if self.key is None or (key != self.key and (not every_call or self.calls - self.last_check >= self.min_gap)):
+        # rate-limited while the weights KEEP changing: some EARLIER forward among the last `min_gap` saw a new generation
+        # too -- whether every forward does (evaluation interleaved with optimizer steps) or two, three, ... forwards
+        # share a generation (anchor / positive / negative evaluated separately, a train step followed by validation
+        # batches: ADVICE r6 -- looking at the previous forward alone never limited those).  A single change after
+        # `min_gap` stable forwards -- a checkpoint loaded after a warm-up -- is measured at once.
+        churning = self.calls - self._last_change < self.min_gap
+        self._seen = key
+        if changed:
+            self._last_change = self.calls
+        if self.key is None or (key != self.key and (not churning or self.calls - self.last_check >= self.min_gap)):
             self.calibrate(model, x, lengths)
         elif self.pending is None and self.calls - self.last_check >= self.recheck and lengths is None:
             self._recheck_async(model, x)

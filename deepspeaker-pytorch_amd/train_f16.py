@@ -192,7 +192,8 @@ def backward_train_f16(eng: Engine, bn_weights: Dict[str, torch.Tensor], pw: Pac
     `overflow_flag` (int32 device tensor [1]): set to 1 at the end of the pass if any filter / fc gradient is inf or NaN
     (the static loss scale was too large for this step); never cleared and never read by the host here -- a step may be
     several passes (three `model(x)` calls, gradient accumulation), so the flag is cleared where it is CONSUMED: by the
-    fused optimizer after its update (optim._FusedBase._consume_skip)."""
+    fused optimizer after its update (optim._FusedBase._consume_skip) or, in a loop stepped by any other optimizer, by the
+    `DeepSpeakerModel.consume_overflow()` / `update_loss_scale()` that loop must call once per step."""
     G = saved.stats["model.bn1"].shape[1]
     grads, buckets = _backward_walk(eng, _F16(eng, G, loss_scale, reducer), bn_weights, pw, saved, ge, reducer,
                                     reduce_gradients, overlap_filter_gradients)

@@ -10,7 +10,9 @@ here.  `GraphedTripletStep` captures all of it once and replays it per batch:
 
 What makes the step capturable (each was a capture error or a silent wrong answer before):
   * the library allocates nothing and never synchronises; the persistent kernels' tile counters come from the caller's
-    workspace (`_native.NativeLib.add_sched_workspace`), one slot per captured launch for good;
+    workspace (`_native.NativeLib.add_sched_workspace`), one slot per captured launch for good -- secured before the
+    capture, outside it (`reserve_sched_slots` with the launches the warm-up counted), and never handed back: a rebuilt
+    step costs a few KB of slots, there is no ABI for returning them;
   * the fused optimizers write their pointer tables with `ds_fill_bytes` (values as kernel arguments) instead of a pinned
     staging copy, whose event torch's host allocator may not query once it was recorded in a capturing stream;
   * the step count that enters Adagrad's decayed learning rate / Adam's bias corrections lives ON THE DEVICE
@@ -37,7 +39,7 @@ from typing import Sequence
 
 import torch
 
-from .model import DeepSpeakerModel, TripletMarginLoss, _require_cuda
+from .model import DeepSpeakerModel, TripletMarginLoss, _require_cuda, get_engine
 
 
 class GraphedTripletStep:
@@ -70,9 +72,13 @@ class GraphedTripletStep:
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(cur)
+        lib = get_engine().lib
+        launched = lib.persistent_launches
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 self._one_step()
+        # persistent launches of ONE step (the warm-up drew from the eager rings; the capture keeps a slot per launch)
+        launched = -(-(lib.persistent_launches - launched) // max(1, warmup))
         cur.wait_stream(side)
         torch.cuda.synchronize(dev)
         with torch.no_grad():
@@ -98,6 +104,9 @@ class GraphedTripletStep:
         model._stat_updates = keep_updates
         torch.cuda.synchronize(dev)
         # ---- capture ----
+        # the slots the capture will keep are secured NOW: inside it the pool cannot be topped up (a dozen or
+        # so rebuilds -- new learning rate, new batch shape -- used a 1024-slot buffer up, and the next capture failed)
+        lib.reserve_sched_slots(dev, launched)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             self.static_loss, self.static_out = self._one_step()
