@@ -17,6 +17,8 @@ all: $(LIB)
 # each; above the default size limit `#pragma unroll` silently stops unrolling, and the register arrays indexed by
 # the loop counter (filter ring, fragment buffers) would then live in scratch memory
 $(OBJD)/conv_mfma_f16_k%.o $(OBJD)/conv_mfma_f16_pk%.o $(OBJD)/conv_block_f16.o: FLAGS += -mllvm -pragma-unroll-threshold=1000000
+# the same for the pipelined walk of the bf16x3 kernel: 25 taps with the pixel items dealt out between their MFMAs
+$(OBJD)/conv_mfma_bf16_k3x3p.o $(OBJD)/conv_mfma_bf16_k5x3p.o: FLAGS += -mllvm -pragma-unroll-threshold=1000000
 
 $(OBJD)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJD)

@@ -99,6 +99,7 @@ static double frag_read_cost(int MT, int NI, int RT, int Wc, int IS, int rows_in
 
 // ---- host-side plan: the shared tile search (conv_plan.h) over the rows of kCfgB (conv_mfma_bf16_kernel.h) ----
 static int g_forced_cfg_b = -1;      // tuning hook (tools/bf16_cfg_ab.py): plan with this tile configuration only
+static int g_walk_b = 0;             // tuning hook (ds_conv_bf16_set_walk): 0 = the planner's choice, 1 = classic, 2 = pipelined
 
 // what a caller of plan_bf16 lets it choose from beyond the rows of kCfgB
 constexpr int kPlanLatRows = 1;      // the caller can launch a latency row (kCfgBLat): the forced-configuration hook may name one
@@ -108,8 +109,10 @@ constexpr int kPlanLatency = 2;      // DS_CONV_PLAN_LATENCY: plan a launch that
 // buffers alias, then the out_off [MT], seg_lo / seg_cnt [NI] and statistics [WM][NTILE][2] tables.  The launch asks
 // for kLdsSlackB bytes more than this; the configurations' caps are compared against this figure.
 constexpr size_t kLdsSlackB = 16;
-static size_t plan_lds_bytes(const TileCfgB &cf, size_t tile_pix, bool x3, int NI) {
-    return std::max(tile_pix * PSB * (x3 ? 2 : 1), cf.epi_bytes()) + (size_t)cf.MT() * 4 + (size_t)NI * 8 + (size_t)cf.WM * cf.NTILE() * 8;
+// The pipelined walk (`pipe`) holds two such tiles.
+static size_t plan_lds_bytes(const TileCfgB &cf, size_t tile_pix, bool x3, int NI, bool pipe = false) {
+    return std::max(tile_pix * PSB * (x3 ? 2 : 1) * (pipe ? 2 : 1), cf.epi_bytes()) + (size_t)cf.MT() * 4 + (size_t)NI * 8 +
+           (size_t)cf.WM * cf.NTILE() * 8;
 }
 
 // `s` describes the tile grid: input [B,H,W,Cin], KS x KS taps, stride s->stride, output grid Ho x Wo computed
@@ -127,6 +130,12 @@ static size_t plan_lds_bytes(const TileCfgB &cf, size_t tile_pix, bool x3, int N
 // for the same latency), then to the first search's objective.  Every row
 // accumulates an output element over the same k-steps in the same order (hi*lo, lo*hi, hi*hi per step), so the choice
 // of row never changes a bit of the result.
+//
+// The walk: exactly the launches the flag re-plans -- bf16x3 forward launches that put less than one wave on every SIMD
+// -- take the pipelined walk of the kernel (PIPE; same bits again) where the planned row has one (ds_bf16_has_pipe) and
+// its two pixel tiles fit the LDS; every other launch keeps the classic walk.  ds_conv_bf16_set_walk(1) keeps it
+// everywhere; (2) asks for the pipelined walk in every bf16x3 forward launch and is an error
+// (DS_ERR_UNSUPPORTED), not a silent classic walk, where the row has none or the tiles do not fit.
 static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride = 1, int out_h0 = 0, int out_w0 = 0,
                      int out_H = 0, int out_W = 0, int grid_H = 0, int grid_W = 0, int mode = 0) {
     int Ho, Wo;
@@ -182,7 +191,8 @@ static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride 
     };
     const bool forced_lat = (mode & kPlanLatRows) && g_forced_cfg_b >= kNumCfgB;
     for (int c = 0; c < (forced_lat ? kNumCfgBAll : kNumCfgB); ++c) search(c);
-    if ((mode & kPlanLatency) && x3 && g_forced_cfg_b < 0 && bc >= 0 && bwaves < kPlanSIMDs) {
+    const bool sub_chip = (mode & kPlanLatency) && x3 && bc >= 0 && bwaves < kPlanSIMDs;
+    if (sub_chip && g_forced_cfg_b < 0) {
         latency = true;
         best = -1.0;
         bc = -1;
@@ -208,7 +218,13 @@ static int plan_bf16(PlanB &pl, const ds_conv_shape *s, bool x3, int out_stride 
     k.pitch = best_pitch;
     k.seg_pix = k.rows_in * k.pitch;
     k.y_bytes = (unsigned)((long long)s->B * yH * yW * s->Cout * 4);
-    pl.lds_bytes = plan_lds_bytes(cf, (size_t)k.NI * k.seg_pix, x3, k.NI) + kLdsSlackB;
+    pl.pipe = 0;
+    if (x3 && (mode & kPlanLatRows) && (g_walk_b == 2 || (g_walk_b == 0 && sub_chip))) {
+        const bool can = ds_bf16_has_pipe(bc) && plan_lds_bytes(cf, (size_t)k.NI * k.seg_pix, true, k.NI, true) + kLdsSlackB <= kLdsCapPipeB;
+        if (!can && g_walk_b == 2) return DS_ERR_UNSUPPORTED;
+        pl.pipe = can;
+    }
+    pl.lds_bytes = plan_lds_bytes(cf, (size_t)k.NI * k.seg_pix, x3, k.NI, pl.pipe != 0) + kLdsSlackB;
     pl.nit = ds_ceil_div(k.NI * std::min(k.rows_in, s->H) * s->W * (CKB / 4), cf.NTHR());
     // a plain launch until a fused entry point says otherwise: no BatchNorm-backward epilogue
     k.bn_z = k.bn_mean = k.bn_invstd = k.bn_msc = k.bn_msh = nullptr;
@@ -227,6 +243,10 @@ static void set_operands(ConvKB &k, const float *x, const void *w_hi, const void
 // kernel size x arithmetic -> the translation unit that holds those instantiations
 template <int KS, bool X3>
 static void launch_b(const PlanB &pl, void *stream) {
+    if (pl.pipe) {                      // the pipelined walk: bf16x3 only (plan_bf16)
+        if (KS == 3) ds_bf16_launch_k3x3p(pl, stream); else ds_bf16_launch_k5x3p(pl, stream);
+        return;
+    }
     if (pl.cfg >= kNumCfgB) {           // a latency row: bf16x3 only (plan_bf16 offers them to no other arithmetic)
         if (KS == 3) ds_bf16_launch_k3x3l(pl, stream); else ds_bf16_launch_k5x3l(pl, stream);
         return;
@@ -303,6 +323,16 @@ extern "C" int ds_conv_bf16_stats_rows(const ds_conv_shape *s, int x3) {
 // tuning hook: cfg in [0, 9) = plan every bf16 convolution with that tile configuration, 9 and 10 = the latency rows
 // (bf16x3 forward launches only: every other launch is then refused); anything else = the planner's choice
 extern "C" void ds_conv_bf16_set_forced_cfg(int cfg) { g_forced_cfg_b = (cfg >= 0 && cfg < kNumCfgBAll) ? cfg : -1; }
+
+// tuning hook: the walk of the bf16x3 forward launches (see plan_bf16); anything but 1 and 2 = the planner's choice
+extern "C" void ds_conv_bf16_set_walk(int walk) { g_walk_b = (walk == 1 || walk == 2) ? walk : 0; }
+
+// the walk ds_conv_fwd_bf16 would launch `s` with under `flags`: 1 = classic, 2 = pipelined, or an error code
+extern "C" int ds_conv_bf16_plan_walk(const ds_conv_shape *s, int x3, int flags) {
+    PlanB pl;
+    const int rc = plan_bf16(pl, s, x3 != 0, 1, 0, 0, 0, 0, 0, 0, fwd_plan_mode(flags));
+    return rc == DS_OK ? (pl.pipe ? 2 : 1) : rc;
+}
 
 extern "C" int ds_conv_bf16_plan_describe(const ds_conv_shape *s, int x3, int *out8) {
     return ds_conv_bf16_plan_describe_hinted(s, x3, 0, out8);

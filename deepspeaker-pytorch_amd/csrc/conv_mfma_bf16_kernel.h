@@ -43,6 +43,7 @@ struct ConvKB {
 
 struct PlanB {
     int cfg, grid, n_mtiles, nit;
+    int pipe;                       // the pipelined walk (PIPE of the kernel): two pixel tiles in lds_bytes
     size_t lds_bytes;
     ConvKB k;
 };
@@ -91,6 +92,12 @@ constexpr TileCfgB kCfgBLat[kNumCfgBLat] = {
 constexpr int kNumCfgBAll = kNumCfgB + kNumCfgBLat;
 constexpr const TileCfgB &ds_bf16_cfg(int cfg) { return cfg < kNumCfgB ? kCfgB[cfg] : kCfgBLat[cfg - kNumCfgB]; }
 
+// The pipelined walk (PIPE of the kernel) is built for the rows a launch of less than one wave per SIMD is planned
+// onto: the latency rows and the 128 x 64 row of kCfgB.  Its two pixel tiles may take more than a row's lds_cap (which
+// sizes ONE tile): the launch opts into the whole LDS, and a workgroup of such a launch has its CU to itself anyway.
+constexpr bool ds_bf16_has_pipe(int cfg) { return cfg == 0 || (cfg >= kNumCfgB && cfg < kNumCfgBAll); }
+constexpr size_t kLdsCapPipeB = 160 * 1024 - 64;
+
 // one entry point per translation unit (kernel size x arithmetic)
 void ds_bf16_launch_k3x3(const PlanB &pl, void *stream);
 void ds_bf16_launch_k5x3(const PlanB &pl, void *stream);
@@ -99,6 +106,8 @@ void ds_bf16_launch_k5x1(const PlanB &pl, void *stream);
 void ds_bf16_launch_k3x3g(const PlanB &pl, void *stream);      // 3x3 bf16x3 with the BatchNorm-backward epilogue
 void ds_bf16_launch_k3x3l(const PlanB &pl, void *stream);      // the latency rows (pl.cfg >= kNumCfgB), bf16x3
 void ds_bf16_launch_k5x3l(const PlanB &pl, void *stream);
+void ds_bf16_launch_k3x3p(const PlanB &pl, void *stream);      // the pipelined walk (pl.pipe, ds_bf16_has_pipe(pl.cfg)), bf16x3
+void ds_bf16_launch_k5x3p(const PlanB &pl, void *stream);
 
 #ifdef DS_BF16_KERNEL_TU
 namespace {
@@ -109,13 +118,22 @@ namespace {
 // tiles, where 16 slots would not fit next to the accumulators).
 // BNB: the epilogue is the first half of a BatchNorm backward (see ConvKB): y = (acc [+ res]) * [0 < z*msc+msh < 20]
 // and the per-tile partial sums are { sum y, sum y * xhat }, xhat = (z - mean) * invstd, instead of { sum, sum sq }.
-template <int KS, int MSUB, int NSUB, int WM, int WN, bool X3, int NIT, bool PREF, bool BNB = false>
+// PIPE (bf16x3, register tiles of at most two sub-tiles): the walk for launches that put at most one wave on a SIMD, where
+// no other wave covers this one's LDS, barrier and L2 latency.  The pixel tile is double-buffered in LDS: while the taps
+// of chunk c read buffer c & 1, the pixels of chunk c + 1 are converted and stored into the other buffer between the
+// MFMAs (and the pixels of chunk c + 2 requested into the registers that frees), so one LDS-only barrier per chunk
+// replaces two __syncthreads(); the next tap's pixel fragments are fetched in front of this tap's MFMAs and the filter
+// ring is refilled behind them.  Every output element is accumulated over the same k-steps in the same term order as
+// in the classic walk: the results are the same bits.
+template <int KS, int MSUB, int NSUB, int WM, int WN, bool X3, int NIT, bool PREF, bool BNB = false, bool PIPE = false>
 __global__ void __launch_bounds__(WM * WN * 64) conv_mfma_bf16_kernel(const ConvKB p) {
     constexpr int NTHR = WM * WN * 64;
     constexpr int MT = MSUB * WM * 32;
     constexpr int NTILE = NSUB * WN * 32;
     constexpr int NT = KS * KS;
-    constexpr int RING = (KS == 3) ? (MSUB <= 2 ? 9 : 3) : (KS == 5 ? 5 : 1);
+    // PIPE, 5x5 with a single sub-tile: a tap is 3 MFMAs (~100 cycles), and a refill 4 taps ahead would be shorter than a
+    // filter slice's way from beyond the L2; the ring holds a whole chunk's taps there
+    constexpr int RING = (KS == 3) ? (MSUB <= 2 ? 9 : 3) : (KS == 5 ? ((PIPE && MSUB * NSUB == 1) ? 25 : 5) : 1);
     // 160x64 register tiles run one wave per SIMD: nothing else hides LDS latency there, so the next
     // tap's pixel fragments are fetched before (X3: in between) this tap's matrix work
     constexpr bool APREF = (MSUB * NSUB >= 8);
@@ -133,7 +151,8 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_mfma_bf16_kernel(const Conv
     // the pixel-tile region doubles as the epilogue's transposition buffers (32 x (NSUB*32+4) floats per wave)
     constexpr int EPI_BYTES = WM * WN * 32 * (NSUB * 32 + 4) * 4;
     const int tile_bytes = (X3 ? 2 : 1) * tile_pix * PSB;
-    const int stage_bytes = tile_bytes > EPI_BYTES ? tile_bytes : EPI_BYTES;
+    const int tiles_bytes = (PIPE ? 2 : 1) * tile_bytes;       // PIPE: two pixel tiles, [buffer][hi | lo][tile_pix][PSB]
+    const int stage_bytes = tiles_bytes > EPI_BYTES ? tiles_bytes : EPI_BYTES;
     char *lds_hi = lds;                                        // [tile_pix][PSB]
     char *lds_lo = lds + (X3 ? tile_pix * PSB : 0);
     int *out_off = (int *)(lds + stage_bytes);                 // [MT]
@@ -238,7 +257,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_mfma_bf16_kernel(const Conv
     }
     // ---- everything below overlaps the first chunk's loads ----
     // Only in-image pixels are ever staged: the zero halo (and the row padding) is written once, here.
-    for (int i = tid; i < tile_bytes / 16; i += NTHR) *(f32x4 *)(lds + 16 * i) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = tid; i < tiles_bytes / 16; i += NTHR) *(f32x4 *)(lds + 16 * i) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     for (int m = tid; m < MT; m += NTHR) {
         const int seg = ds_div_small(m, pix_per_seg, rcp_pps);
         const int rem = m - seg * pix_per_seg;
@@ -284,6 +303,95 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_mfma_bf16_kernel(const Conv
         for (int it = 0; it < NIT; ++it) split_item(it);
     }
 
+    if constexpr (PIPE) {
+        static_assert(X3 && PREF && !BNB && MSUB * NSUB <= 2 && NT % RING == 0, "the pipelined walk: bf16x3, small register tiles");
+        constexpr int NM = 3 * MSUB * NSUB, NR = 2 * NSUB;
+        const int plane = tile_pix * PSB;       // the lo records of a tile follow its hi records
+        auto tap_off = [&](int tt) {
+            const int kw = tt % KS;
+            return ((tt / KS) * p.pitch + (p.IS == 2 ? (kw & 1) * p.half + (kw >> 1) : kw)) * PSB;
+        };
+        // item `it`: the pixels held in st -> hi / lo records of the tile at `buf`; st then takes the item's pixels of
+        // chunk cn, which have a whole chunk's matrix work to arrive
+        auto put_item = [&](int it, char *buf, int cn) {
+            const f32x4 v = st[it];
+            bf16x4 h, l;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                h[j] = (__bf16)v[j];
+                l[j] = (__bf16)(v[j] - (float)h[j]);
+            }
+            *(bf16x4 *)(buf + l_off[it]) = h;
+            *(bf16x4 *)(buf + plane + l_off[it]) = l;
+            st[it] = *(const f32x4 *)(p.x + g_off[it] + cn * CKB);
+        };
+        __syncthreads();                        // both tiles are zeroed
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) put_item(it, lds, n_chunks > 1 ? 1 : 0);
+        __syncthreads();
+        // ONE barrier per chunk, executed by every wave n_chunks times whatever n_chunks is: behind it every wave has
+        // read the last fragment of buffer chunk & 1 (the next chunk overwrites it) and has stored its share of the
+        // other buffer (the next chunk reads it).  The last chunk stores pixels nobody reads into the free buffer.
+        for (int chunk = 0; chunk < n_chunks; ++chunk) {
+            const int rd = (chunk & 1) * tile_bytes;
+            char *wr = lds + (tile_bytes - rd);
+            const int cn = chunk + 2 < n_chunks ? chunk + 2 : n_chunks - 1;
+            const int g0 = chunk * NT;
+            const char *a_cur[MSUB];
+            bf16x8 a_hi[2][MSUB], a_lo[2][MSUB];
+#pragma unroll
+            for (int ms = 0; ms < MSUB; ++ms) {
+                a_cur[ms] = lds + rd + a_off[ms];
+                a_lo[0][ms] = *(const bf16x8 *)(a_cur[ms] + plane + tap_off(0));
+                a_hi[0][ms] = *(const bf16x8 *)(a_cur[ms] + tap_off(0));
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int slot = t % RING, cur = t & 1, rslot = (t + RING - 1) % RING;
+                __builtin_amdgcn_sched_barrier(0);
+                // the next tap's fragments: in flight for the three (six) MFMAs of this tap
+                if (t + 1 < NT) {
+                    const int toff = tap_off(t + 1);
+#pragma unroll
+                    for (int ms = 0; ms < MSUB; ++ms) a_lo[cur ^ 1][ms] = *(const bf16x8 *)(a_cur[ms] + plane + toff);
+#pragma unroll
+                    for (int ms = 0; ms < MSUB; ++ms) a_hi[cur ^ 1][ms] = *(const bf16x8 *)(a_cur[ms] + toff);
+                }
+                int gn = g0 + t - 1 + RING;                 // refills the slot the previous tap consumed
+                gn = gn < last_tap ? gn : last_tap;
+                const __bf16 *rhi = p.w_hi + lane_w + (size_t)gn * w_tap_stride;
+                const __bf16 *rlo = p.w_lo + lane_w + (size_t)gn * w_tap_stride;
+                const int i0 = (NIT * t) / NT, i1 = (NIT * (t + 1)) / NT;      // this tap's share of the pixel items
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int q = 0; q < NM; ++q) {
+                    const int term = q / (MSUB * NSUB), ms = (q % (MSUB * NSUB)) / NSUB, ns = q % NSUB;
+                    if (term == 0) acc[ms][ns] = ds_mfma_32x32x16_bf16(bq_hi[slot][ns], a_lo[cur][ms], acc[ms][ns]);
+                    else if (term == 1) acc[ms][ns] = ds_mfma_32x32x16_bf16(bq_lo[slot][ns], a_hi[cur][ms], acc[ms][ns]);
+                    else acc[ms][ns] = ds_mfma_32x32x16_bf16(bq_hi[slot][ns], a_hi[cur][ms], acc[ms][ns]);
+                    if (t > 0 && q < NR) {
+                        if (q & 1) bq_lo[rslot][q >> 1] = *(const bf16x8 *)(rlo + (size_t)(q >> 1) * 32 * CKB);
+                        else bq_hi[rslot][q >> 1] = *(const bf16x8 *)(rhi + (size_t)(q >> 1) * 32 * CKB);
+                    }
+#pragma unroll
+                    for (int it = i0; it < i1; ++it)
+                        if (NR + (it - i0) % (NM - NR) == q) put_item(it, wr, cn);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            {
+                int gn = g0 + NT - 1 + RING;
+                gn = gn < last_tap ? gn : last_tap;
+#pragma unroll
+                for (int ns = 0; ns < NSUB; ++ns) {
+                    const size_t o = lane_w + (size_t)gn * w_tap_stride + (size_t)ns * 32 * CKB;
+                    bq_hi[(NT - 1) % RING][ns] = *(const bf16x8 *)(p.w_hi + o);
+                    bq_lo[(NT - 1) % RING][ns] = *(const bf16x8 *)(p.w_lo + o);
+                }
+            }
+            ds_lds_barrier();
+        }
+    } else                                     // the classic walk: one pixel tile, two barriers per chunk
     for (int chunk = 0; chunk < n_chunks; ++chunk) {
         __syncthreads();                       // previous chunk's fragment reads are done
         if constexpr (!PREF) {
@@ -639,6 +747,29 @@ static void launch_lat_b(const PlanB &pl, void *stream) {
         if (pl.cfg - kNumCfgB == N) launch_nit_b<KS, cf.MSUB, cf.NSUB, cf.WM, cf.WN, true>(pl, stream);
         else launch_lat_b<KS, N + 1>(pl, stream);
     }
+}
+
+// the pipelined walk of one row: always with the register prefetch, whatever the items per thread (the launch has a
+// SIMD's whole register file to itself)
+template <int KS, int MSUB, int NSUB, int WM, int WN>
+static void launch_pipe_nit_b(const PlanB &pl, void *stream) {
+    static_assert(WM * WN * 64 == 256, "256 threads");
+    if (pl.nit <= 4)
+        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, NSUB, WM, WN, true, 4, true, false, true>), pl.grid, 256, pl.lds_bytes, stream, pl.k);
+    else if (pl.nit <= 8)
+        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, NSUB, WM, WN, true, 8, true, false, true>), pl.grid, 256, pl.lds_bytes, stream, pl.k);
+    else
+        DS_LAUNCH_BIG_LDS((conv_mfma_bf16_kernel<KS, MSUB, NSUB, WM, WN, true, 16, true, false, true>), pl.grid, 256, pl.lds_bytes, stream, pl.k);
+}
+
+// pl.cfg -> the rows of ds_bf16_has_pipe
+template <int KS>
+static void launch_pipe_b(const PlanB &pl, void *stream) {
+    constexpr TileCfgB c0 = kCfgB[0], l0 = kCfgBLat[0], l1 = kCfgBLat[1];
+    static_assert(kNumCfgBLat == 2 && ds_bf16_has_pipe(0) && ds_bf16_has_pipe(kNumCfgB) && ds_bf16_has_pipe(kNumCfgB + 1), "");
+    if (pl.cfg == 0) launch_pipe_nit_b<KS, c0.MSUB, c0.NSUB, c0.WM, c0.WN>(pl, stream);
+    else if (pl.cfg == kNumCfgB) launch_pipe_nit_b<KS, l0.MSUB, l0.NSUB, l0.WM, l0.WN>(pl, stream);
+    else if (pl.cfg == kNumCfgB + 1) launch_pipe_nit_b<KS, l1.MSUB, l1.NSUB, l1.WM, l1.WN>(pl, stream);
 }
 
 }  // namespace

@@ -230,6 +230,13 @@ int ds_conv_bf16_plan_describe(const ds_conv_shape *s, int x3, int *out8);
 /* the same under the DS_CONV_PLAN_LATENCY bit of `flags` (what ds_conv_fwd_bf16 would launch) */
 int ds_conv_bf16_plan_describe_hinted(const ds_conv_shape *s, int x3, int flags, int *out8);
 void ds_conv_bf16_set_forced_cfg(int cfg);  /* tuning hook, as ds_conv_f16_set_forced_cfg */
+/* tuning hook: how the bf16x3 forward launches walk the contraction.  0 (default): the pipelined walk (two pixel tiles
+ * in LDS, one barrier per chunk, fragment and filter fetches inside the MFMA stream) for the launches
+ * DS_CONV_PLAN_LATENCY re-plans, the classic walk for every other; 1: classic everywhere; 2: pipelined for every
+ * bf16x3 forward launch -- DS_ERR_UNSUPPORTED where the planned tile has no such kernel.  Both walks give the same bits. */
+void ds_conv_bf16_set_walk(int walk);
+/* the walk ds_conv_fwd_bf16 would take under `flags`: 1 = classic, 2 = pipelined, or an error code */
+int ds_conv_bf16_plan_walk(const ds_conv_shape *s, int x3, int flags);
 int ds_conv_fwd_bf16(const ds_conv_shape *s, const float *x, const void *w_hi, const void *w_lo,
                      const float *scale, const float *shift, const float *residual, float *y,
                      float *stats_partial, int flags, void *stream);
