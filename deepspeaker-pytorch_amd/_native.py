@@ -183,6 +183,9 @@ _SIGNATURES = {
     "ds_nearest_rescore_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "ds_segment_mean_rows_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P]),
     "ds_rank_hits_i32": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
+    "ds_cohort_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int, c_int]),
+    "ds_cohort_stats_f32": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "ds_score_norm_apply_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_float, _P, c_int, _P]),
     "ds_roc_sweep_f32": (c_int, [_P, _P, c_int, c_float, c_float, c_int, c_int, c_int, _P, _P, _P, _P]),
     "ds_assemble_crops_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "ds_optim_chunk_elems": (c_int, []),

@@ -12,46 +12,17 @@
 #include <ds_device.h>
 #include "ds_common.h"
 #include "row_distance.h"
+#include "screen_tile.h"
 
 namespace {
 
-constexpr int NQ = 64;              // queries per workgroup
-constexpr int NG = 128;             // gallery rows per tile: 32 per wave
-constexpr int KC = 32;              // dimensions per staged chunk
-constexpr int KP = KC + 4;          // row pitch of the staged chunk in floats (16-byte aligned, conflict-free b128 reads)
-constexpr int SP = NG + 4;          // row pitch of the screening tile
-constexpr int STAGE_FLOATS = (NQ + NG) * KP;
-constexpr int TILE_FLOATS = NQ * SP > STAGE_FLOATS ? NQ * SP : STAGE_FLOATS;      // the two alias each other
-constexpr int SLOTS = (NQ + NG) * (KC / 4) / 256;                                 // float4 per thread and chunk
+// NQ, NG, the staging constants, row_sqnorm_kernel and the tile GEMM with its screening epilogue: screen_tile.h
 constexpr int MAX_SPLITS = 64;
 
 __device__ __forceinline__ bool pair_less(float d, int i, float d2, int i2) { return d < d2 || (d == d2 && i < i2); }
 
-// norms[r] = sum_k x[r,k]^2: one wavefront per row, lane l sums dimensions l, l + 64, ... in order, then the butterfly.
-// The value of a row depends on nothing but the row.
-__global__ void __launch_bounds__(256) row_sqnorm_kernel(const float *q, const float *g, float *qn, float *gn, int N,
-                                                         int M, int D) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const bool live = row < N + M;
-    const float *src = !live ? q : row < N ? q + (size_t)row * D : g + (size_t)(row - N) * D;
-    float ss = 0.f;
-    for (int k = lane; k < D; k += 64) {
-        const float v = src[k];
-        ss = __builtin_fmaf(v, v, ss);
-    }
-    ss = wave_sum(ss);
-    if (live && lane == 0) {
-        if (row < N) qn[row] = ss;
-        else gn[row - N] = ss;
-    }
-}
-
 // A workgroup owns NQ queries and walks the NG-row tiles [tile0, tile1) of one gallery split.
-//   GEMM: wave w owns gallery rows 32 w .. 32 w + 31 of the tile and both 32-query halves (two 32x32 accumulators).  A
-//   chunk of KC dimensions of the 64 + 128 rows is staged through LDS (next chunk prefetched into registers); a lane
-//   reads 4 consecutive dimensions of its row with one b128 and feeds them to 4 MFMAs, so the dimensions of a pair are
-//   always accumulated in the same order (per 8: 0, 4, 1, 5, 2, 6, 3, 7) -- wherever the pair falls.
+//   GEMM and screening epilogue: screen_tile (screen_tile.h), shared with the cohort statistics of score_norm.hip.
 //   Top-k: the tile's screening values go to LDS (over the dead staging buffer); four threads per query test 32
 //   candidates each against the query's current k-th best, and the query's owner thread inserts the few that pass
 //   into the sorted list it keeps in LDS.
@@ -72,13 +43,12 @@ __global__ void __launch_bounds__(256) nearest_screen_kernel(const float *q, con
     float *list_d = (float *)(thr_i + NQ);                 // [NQ][kp]
     int *list_i = (int *)(list_d + NQ * kp);               // [NQ][kp]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int qb = blockIdx.x % n_qblocks, split = blockIdx.x / n_qblocks;
     const int q0 = qb * NQ;
     const int n_tiles = (M + NG - 1) / NG;
     const int tile0 = split * tiles_per_split;
     const int tile1 = tile0 + tiles_per_split < n_tiles ? tile0 + tiles_per_split : n_tiles;
-    const int n_chunks = (D + KC - 1) / KC;
 
     if (tid < NQ) {
         qn_s[tid] = q0 + tid < N ? qn[q0 + tid] : 0.f;
@@ -91,70 +61,15 @@ __global__ void __launch_bounds__(256) nearest_screen_kernel(const float *q, con
     const long long my_qlab = (mode != 0 && q0 + oq < N) ? qlab[q0 + oq] : 0;
 
     f32x4 pre[SLOTS];
-    auto fetch = [&](int tile, int k0) {
-#pragma unroll
-        for (int it = 0; it < SLOTS; ++it) {
-            const int i = tid + it * 256;
-            const int row = i / (KC / 4), c = i - row * (KC / 4);
-            const int kk = k0 + c * 4;
-            pre[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (kk < D) {
-                if (row < NQ) {
-                    if (q0 + row < N) pre[it] = *(const f32x4 *)(q + (size_t)(q0 + row) * D + kk);
-                } else {
-                    const long long j = (long long)tile * NG + (row - NQ);
-                    if (j < M) pre[it] = *(const f32x4 *)(g + (size_t)j * D + kk);
-                }
-            }
-        }
-    };
-    if (tile0 < tile1) fetch(tile0, 0);
+    if (tile0 < tile1) screen_fetch(pre, q, g, q0, tile0, 0, N, M, D, tid);
     for (int tile = tile0; tile < tile1; ++tile) {
         const int j0 = tile * NG;
-        f32x16 acc0, acc1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
-        for (int ch = 0; ch < n_chunks; ++ch) {
-            __syncthreads();                               // the previous chunk (or the previous tile's top-k pass) is done
-#pragma unroll
-            for (int it = 0; it < SLOTS; ++it) {
-                const int i = tid + it * 256;
-                const int row = i / (KC / 4), c = i - row * (KC / 4);
-                *(f32x4 *)(stage + row * KP + c * 4) = pre[it];
-            }
-            if (ch == 0 && tid < NG) {                     // this tile's norms and labels (their last readers are behind us)
+        screen_tile(stage, pre, q, g, qn_s, gn_s, q0, tile, tile + 1 < tile1 ? tile + 1 : -1, N, M, D, [&]() {
+            if (tid < NG) {                                // this tile's norms and labels (their last readers are behind us)
                 gn_s[tid] = j0 + tid < M ? gn[j0 + tid] : 0.f;
                 if (mode != 0) glab_s[tid] = j0 + tid < M ? glab[j0 + tid] : 0;
             }
-            __syncthreads();
-            if (ch + 1 < n_chunks) fetch(tile, (ch + 1) * KC);
-            else if (tile + 1 < tile1) fetch(tile + 1, 0);
-            const float *qa = stage + (lane & 31) * KP + 4 * (lane >> 5);
-            const float *ga = stage + (NQ + 32 * wave + (lane & 31)) * KP + 4 * (lane >> 5);
-#pragma unroll
-            for (int st = 0; st < KC / 8; ++st) {
-                const f32x4 a0 = *(const f32x4 *)(qa + 8 * st);
-                const f32x4 a1 = *(const f32x4 *)(qa + 32 * KP + 8 * st);
-                const f32x4 b = *(const f32x4 *)(ga + 8 * st);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    acc0 = ds_mfma_32x32x2_f32(a0[u], b[u], acc0);
-                    acc1 = ds_mfma_32x32x2_f32(a1[u], b[u], acc1);
-                }
-            }
-        }
-        __syncthreads();                                   // every wave is done with the staged rows
-        {
-            const int col = 32 * wave + (lane & 31);
-            const float gnj = gn_s[col];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                stage[row * SP + col] = __builtin_fmaf(-2.0f, acc0[r], qn_s[row] + gnj);
-                stage[(row + 32) * SP + col] = __builtin_fmaf(-2.0f, acc1[r], qn_s[row + 32] + gnj);
-            }
-        }
-        __syncthreads();
+        });
         {   // 32 candidates per thread against the query's current k-th best
             const float td = thr_d[oq];
             const int ti = thr_i[oq];

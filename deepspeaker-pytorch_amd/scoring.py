@@ -6,6 +6,8 @@ are embedded as `crops` fixed-length crops, the distance is taken crop-by-crop a
 threshold) plus the equal error rate the reference never computes.
 `speaker_models` / `nearest` / `identify` = identification, which the reference does not have: enrolled speaker models,
 the k nearest gallery rows of every query (csrc/identify.hip) and rank-1 ... rank-k accuracy.
+`cohort_stats` / `normalise_scores` = score normalisation (Z / T / S / AS-norm, csrc/score_norm.hip) between the raw trial
+score and `evaluate`; `min_dcf` = the minimum detection cost on `evaluate`'s counts.
 """
 from __future__ import annotations
 
@@ -201,3 +203,128 @@ def identify(test_emb: torch.Tensor, models: torch.Tensor, model_labels, test_la
     eng.lib.call("ds_rank_hits_i32", eng._p(idx), eng._p(ml), eng._p(tl), eng._p(hits), n, k, eng._stream(idx))
     h = hits.cpu().numpy()
     return Identification(labels, dist, idx, hits, float(h[0]) / n, float(h[k - 1]) / n)
+
+
+# ---- score normalisation: cohort statistics and Z / T / S / AS-norm (csrc/score_norm.hip) -----------------------------
+COHORT_MAX_M = 32768           # DS_COHORT_MAX_M
+_NORM_KINDS = ("z", "t", "s", "as")
+
+
+@dataclass
+class CohortStats:
+    mean: torch.Tensor                   # [N] float32: mean distance to the selected cohort rows (+inf where count is 0)
+    std: torch.Tensor                    # [N] float32: their population standard deviation (ddof 0)
+    count: torch.Tensor                  # [N] int32: min(top_k, eligible cohort rows)
+    mask: Optional[torch.Tensor] = None  # [N, ceil(M / 32)] int32: bit j % 32 of word j // 32 = cohort row j was selected
+
+
+def cohort_stats(emb: torch.Tensor, cohort: torch.Tensor, top_k: Optional[int] = None, labels=None, cohort_labels=None,
+                 exclude=None, row_block: int = 0, return_mask: bool = False) -> CohortStats:
+    """Mean and standard deviation of every `emb[N, D]` row's distances to its `top_k` closest rows of `cohort[M, D]`
+    (`top_k=None`: to all M -- Z / T / S-norm; a few hundred: the adaptive AS-norm).  The rows are chosen by the
+    screening value of `nearest` (the same bits), exactly and with ties to the lowest index, by a radix select that
+    never holds the N x M matrix; the statistics are over `PairwiseDistance(2)` of the chosen pairs.
+    `exclude="same"` leaves out cohort rows that carry the row's own label (a cohort that contains the speaker),
+    `"other"` keeps only those; both need `labels` and `cohort_labels`.  `row_block`: rows screened at once (0: chosen
+    for the device); the result does not depend on it.  Nothing is read back."""
+    eng = _eng()
+    if exclude not in _EXCLUDE_MODES:
+        raise ValueError("exclude must be None, 'same' or 'other'")
+    q, g = _rows(emb, "emb"), _rows(cohort, "cohort")
+    (n, d), m = q.shape, g.shape[0]
+    if g.shape[1] != d or g.device != q.device:
+        raise ValueError(f"emb {tuple(q.shape)} and cohort {tuple(g.shape)} must share D and the device")
+    if d % 4 != 0 or d > NEAREST_MAX_D:
+        raise ValueError(f"D = {d}: the search takes multiples of 4 up to {NEAREST_MAX_D}")
+    if m > COHORT_MAX_M:
+        raise ValueError(f"M = {m}: a cohort has at most {COHORT_MAX_M} rows")
+    k = m if top_k is None else top_k
+    if not isinstance(k, int) or not 1 <= k <= m:
+        raise ValueError(f"top_k = {top_k!r}: expected None or an integer in 1..M = {m}")
+    if not isinstance(row_block, int) or row_block < 0:
+        raise ValueError(f"row_block = {row_block!r}: expected an integer >= 0")
+    mode = _EXCLUDE_MODES[exclude]
+    ql = gl = None
+    if mode:
+        if labels is None or cohort_labels is None:
+            raise ValueError("exclude needs labels and cohort_labels")
+        ql, gl = _labels(labels, n, "labels", q.device), _labels(cohort_labels, m, "cohort_labels", q.device)
+    nbytes = int(eng.lib.raw("ds_cohort_workspace_bytes")(n, m, d, k, row_block))
+    if nbytes < 0:
+        raise ValueError(f"cohort_stats: unsupported shape N={n} M={m} D={d} K={k}")
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=q.device)
+    mean = torch.empty(n, dtype=torch.float32, device=q.device)
+    std = torch.empty_like(mean)
+    count = torch.empty(n, dtype=torch.int32, device=q.device)
+    mask = torch.empty((n, (m + 31) // 32), dtype=torch.int32, device=q.device) if return_mask else None
+    eng.lib.call("ds_cohort_stats_f32", eng._p(q), eng._p(g), eng._p(ql), eng._p(gl), mode, eng._p(ws), eng._p(mean),
+                 eng._p(std), eng._p(count), eng._p(mask), n, m, d, k, row_block, eng._stream(q))
+    return CohortStats(mean, std, count, mask)
+
+
+def normalise_scores(raw: torch.Tensor, kind: str, enrol_stats: Optional[CohortStats] = None,
+                     test_stats: Optional[CohortStats] = None, enrol_index=None, test_index=None,
+                     min_std: float = 1e-6) -> torch.Tensor:
+    """Normalised trial scores [T] from raw distances `raw[T]` and the two sides' cohort statistics.
+    `kind` "z": (raw - mean_e) / std_e with the enrolment side's statistics; "t": the same with the test side's; "s" and
+    "as": the mean of the two.  "s" and "as" are ONE arithmetic: whether the result is S-norm or the adaptive AS-norm is
+    decided by the `top_k` the statistics were taken with (`cohort_stats(..., top_k=None)` or a few hundred); both
+    spellings are accepted so that a recipe can say what it means.
+    `enrol_index` / `test_index`: int64 [T], the row of the side's statistics each trial uses (many trials share an
+    utterance, so statistics are taken once per distinct embedding); None: trial t uses row t.  A standard deviation
+    below `min_std` is replaced by it.  Distances stay distances: lower still means the same speaker, and `evaluate`
+    applies unchanged (with a signed threshold grid, e.g. thr_start=-10, thr_stop=10)."""
+    eng = _eng()
+    if kind not in _NORM_KINDS:
+        raise ValueError(f"kind = {kind!r}: expected one of {_NORM_KINDS}")
+    need_e, need_t = kind != "t", kind != "z"
+    if need_e and enrol_stats is None:
+        raise ValueError(f"kind {kind!r} needs enrol_stats")
+    if need_t and test_stats is None:
+        raise ValueError(f"kind {kind!r} needs test_stats")
+    if raw.dim() != 1 or raw.dtype != torch.float32 or raw.numel() < 1:
+        raise ValueError(f"raw: expected a [T] float32 tensor, got {tuple(raw.shape)} {raw.dtype}")
+    x = raw.contiguous()
+    t, dev = x.numel(), x.device
+    sides = []
+    for use, stats, index, name in ((need_e, enrol_stats, enrol_index, "enrol"), (need_t, test_stats, test_index, "test")):
+        if not use:
+            continue
+        mu, sd = stats.mean.contiguous(), stats.std.contiguous()
+        if mu.device != dev or sd.device != dev or mu.dtype != torch.float32 or sd.dtype != torch.float32 or \
+                mu.dim() != 1 or mu.shape != sd.shape:
+            raise ValueError(f"{name}_stats: mean and std must be float32 vectors of one length on the scores' device")
+        if index is None:
+            if mu.numel() != t:
+                raise ValueError(f"{name}_stats has {mu.numel()} rows for {t} trials: pass {name}_index")
+            idx = None
+        else:
+            idx = _labels(index, t, f"{name}_index", dev)
+        sides.append((idx, mu, sd))
+    (ia, mu_a, sd_a), (ib, mu_b, sd_b) = sides[0], sides[1] if len(sides) == 2 else (None, None, None)
+    out = torch.empty_like(x)
+    eng.lib.call("ds_score_norm_apply_f32", eng._p(x), eng._p(ia), eng._p(ib), eng._p(mu_a), eng._p(sd_a), eng._p(mu_b),
+                 eng._p(sd_b), float(min_std), eng._p(out), t, eng._stream(x))
+    return out
+
+
+def min_dcf(distances: torch.Tensor, labels: torch.Tensor, p_target: float = 0.01, c_miss: float = 1.0, c_fa: float = 1.0,
+            thr_start: float = 0.0, thr_stop: float = 30.0, thr_step: float = 0.01):
+    """Minimum normalised detection cost over `evaluate`'s threshold grid: (value, threshold).  At a threshold,
+    P_miss = 1 - tp / n_same, P_fa = fp / n_diff and the cost is
+    (c_miss P_miss p_target + c_fa P_fa (1 - p_target)) / min(c_miss p_target, c_fa (1 - p_target)); the first minimum
+    is returned.  A set without same-speaker trials has P_miss = 0 everywhere, one without different-speaker trials
+    P_fa = 0.  Computed on the device from the tp / fp counts `evaluate` leaves there; two scalars are read back."""
+    res = evaluate(distances, labels, thr_start, thr_stop, thr_step)
+    n = distances.numel()
+    n_same = (labels != 0).sum().to(torch.float64)
+    n_diff = n - n_same
+    tp, fp = res.tp.to(torch.float64), res.fp.to(torch.float64)
+    p_miss = torch.where(n_same > 0, 1.0 - tp / n_same.clamp_min(1.0), torch.zeros_like(tp))
+    p_fa = torch.where(n_diff > 0, fp / n_diff.clamp_min(1.0), torch.zeros_like(fp))
+    cost = (c_miss * p_target * p_miss + c_fa * (1.0 - p_target) * p_fa) / min(c_miss * p_target, c_fa * (1.0 - p_target))
+    value = cost.min()
+    grid = torch.arange(cost.numel(), device=cost.device)
+    where = torch.where(cost == value, grid, torch.full_like(grid, cost.numel())).min()
+    both = torch.stack([value, where.to(torch.float64)]).cpu().numpy()
+    return float(both[0]), thr_start + thr_step * float(both[1])

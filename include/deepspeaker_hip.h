@@ -93,7 +93,8 @@ int ds_version(void);            /* 100: round 1; 200: round 2 (fp16 path, group
                                     near-tie refinement, launch-bound timing); 500: round 5; 600: round 6 (caller-owned
                                     scheduler workspace); 700: log-mel filterbank front end (ds_fbank_*); 800: speaker identification
                                     (ds_nearest_*, ds_segment_mean_rows_f32, ds_rank_hits_i32); 900: polyphase resampler
-                                    (ds_resample_plan, ds_resample_poly_f32); 1000: energy VAD (ds_vad_*) */
+                                    (ds_resample_plan, ds_resample_poly_f32); 1000: energy VAD (ds_vad_*); 1100: angular-margin softmax head;
+                                    1200: score normalisation (ds_cohort_*, ds_score_norm_apply_f32) */
 /* launch timing without marker packets: the next MFMA convolution / filter-gradient launch of the calling thread
  * records its own execution into the armed pair (hipExtLaunchKernelGGL); ds_launch_timing_end() disarms and returns
  * how many such launches happened since arming (1 = the timed call was a single kernel) */
@@ -606,6 +607,34 @@ int ds_segment_mean_rows_f32(const float *emb, const long long *offsets, float *
                              float alpha, float eps, void *stream);
 int ds_rank_hits_i32(const long long *index, const long long *gallery_label, const long long *query_label, int *hits,
                      int N, int k, void *stream);
+
+/* ---- score normalisation (csrc/score_norm.hip): Z / T / S / AS-norm ----
+ * ds_cohort_stats_f32: for each row of emb[N,D] the min(K, eligible) rows of cohort[M,D] (row-major f32, 16-byte
+ *   aligned) with the smallest SCREENING value s -- the value of ds_nearest_topk_f32, bit for bit: both run one function
+ *   (csrc/screen_tile.h) -- ordered by (s, cohort index), ties at the K-th value to the lowest indices; then
+ *   mean[n] / std[n] = mean and population standard deviation (ddof 0) of the DISTANCES to those rows, recomputed by
+ *   direct differences in the arithmetic of ds_pairwise_distance_f32 (eps = 1e-4 / D inside the root) and reduced in two
+ *   passes (mean, then sum (d - mean)^2) in a fixed order over the index-ordered selection; count[n] = how many rows.
+ *   K == M: every eligible row (Z / T / S-norm); K < M: the adaptive forms.  The selection is an exact radix select
+ *   over the row's M values held in LDS as order-preserving keys (negative s included), which sets DS_COHORT_MAX_M.
+ *   mode / labels as ds_nearest_topk_f32 (0: all rows; 1: skip rows with the row's own label; 2: only those); a row
+ *   with fewer than K eligible cohort rows takes them all, with none: count 0, mean +inf, std 0.
+ *   selected: NULL, or int32 [N, ceil(M / 32)]: bit (j % 32) of word j / 32 is set iff cohort row j was selected.
+ *   row_block: rows whose screening values are alive at once, [row_block x M] in the workspace (never N x M); 0 = chosen
+ *   by the library.  mean, std and selected are bit-identical whatever N, row_block or the position in the batch.
+ *   1 <= K <= M <= DS_COHORT_MAX_M, D % 4 == 0, D <= DS_NEAREST_MAX_D, else DS_ERR_BAD_SHAPE (workspace query: -1).
+ *   workspace: ds_cohort_workspace_bytes(N, M, D, K, row_block) bytes, 16-byte aligned.
+ * ds_score_norm_apply_f32: out[t] = ((raw[t] - mean_a[ia]) / max(std_a[ia], min_std)
+ *   + (raw[t] - mean_b[ib]) / max(std_b[ib], min_std)) / 2 with ia = a_index[t], ib = b_index[t] (int64 rows of the
+ *   statistics tables; NULL: t itself); mean_b and std_b both NULL: the first term alone, without the 1/2. */
+#define DS_COHORT_MAX_M 32768
+long long ds_cohort_workspace_bytes(int N, int M, int D, int K, int row_block);
+int ds_cohort_stats_f32(const float *emb, const float *cohort, const long long *emb_label, const long long *cohort_label,
+                        int mode, void *workspace, float *mean, float *std, int *count, int *selected, int N, int M,
+                        int D, int K, int row_block, void *stream);
+int ds_score_norm_apply_f32(const float *raw, const long long *a_index, const long long *b_index, const float *mean_a,
+                            const float *std_a, const float *mean_b, const float *std_b, float min_std, float *out, int T,
+                            void *stream);
 
 /* ---- verification scoring on the device --------------------------------------
  * ds_group_mean_f32: score of a trial = mean over G crop-pair distances (train_triplet.py:347-350).
