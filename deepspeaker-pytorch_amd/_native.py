@@ -220,6 +220,11 @@ _SIGNATURES = {
     "ds_vad_decide": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, c_double, _P, _P, _P, _P, _P]),
     "ds_vad_scan": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P]),
     "ds_vad_select_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "ds_augment_plan": (c_int, [_P, c_int, _P, _P]),
+    "ds_augment_workspace_bytes": (c_longlong, [c_int]),
+    "ds_augment_reverb_f32": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
+    "ds_augment_mix_f32": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, _P]),
+    "ds_augment_level_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
 }
 
 

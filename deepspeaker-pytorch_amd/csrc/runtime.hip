@@ -99,6 +99,7 @@ extern "C" long long ds_sched_free_slots(void) {
 }
 
 /* ds_version history:
+ *   1300  waveform augmentation: reverberation, noise at an SNR, level (augment.hip)
  *   1200  score normalisation: cohort statistics by radix select (score_norm.hip)
  *   1100  angular-margin softmax head (margin_head.hip)
  *   1000  energy VAD (vad.hip)
@@ -111,7 +112,7 @@ extern "C" long long ds_sched_free_slots(void) {
  *    301  + ds_conv_dgrad_bnbwd_bf16, ds_bn_bwd_group_finish_f32
  *    300  round-3 ABI: split grouped BatchNorm backward for data parallelism, grouped f64 sums
  */
-extern "C" int ds_version(void) { return 1200; }
+extern "C" int ds_version(void) { return 1300; }
 
 // ---- launch timing (see DS_LAUNCH_BIG_LDS in ds_device.h) ----
 extern "C" int ds_event_create(void **out_event) {

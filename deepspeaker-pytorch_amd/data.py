@@ -38,15 +38,17 @@ class FeatureStore:
 
     @classmethod
     def from_waveforms(cls, waveforms, config=None, normalize="mean", lengths=None, *, orig_rate=None,
-                       channels=1, vad=None) -> "FeatureStore":
+                       channels=1, vad=None, augment=None) -> "FeatureStore":
         """The resident corpus straight from audio: `features.log_mel_fbank` of the waveforms (a sequence of 1-D float32
         / int16 device tensors, or one packed tensor with host `lengths`), kept where it was computed -- no host copy.
         `orig_rate` / `channels`: audio at another rate or with interleaved channels is resampled and mixed down on the
         device first (`features.resample`).  `vad`: a `features.VadConfig` keeps only the voiced frames; an utterance
-        without one has length 0 and its crops are zeros."""
+        without one has length 0 and its crops are zeros.  `augment`: a `features.AugmentPlan` reverberates the
+        waveforms and mixes noise into them on the device before the features are made (`features.augment`)."""
         from .features import FbankConfig, log_mel_fbank
         feats, offsets = log_mel_fbank(waveforms, FbankConfig() if config is None else config, normalize=normalize,
-                                       lengths=lengths, orig_rate=orig_rate, channels=channels, vad=vad)
+                                       lengths=lengths, orig_rate=orig_rate, channels=channels, vad=vad,
+                                       augment=augment)
         store = cls.__new__(cls)
         store.offsets = offsets
         store.n_feat = feats.shape[1]

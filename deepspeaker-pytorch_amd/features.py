@@ -15,6 +15,11 @@ polyphase filter with SciPy's `resample_poly` design.  Decoding files stays on t
 Recordings with silence in them go through an energy voice-activity decision (csrc/vad.hip: `voiced_frames`,
 `select_frames`, the `vad=` keyword of `log_mel_fbank`): only the voiced frames become rows, and the normalisation runs
 over what was kept.
+
+Training utterances are augmented on the device (csrc/augment.hip: `SampleBank`, `AugmentPlan`, `draw_augmentation`,
+`augment`, the `augment=` keyword of `log_mel_fbank`): convolved with a room impulse response and mixed with noise clips
+at drawn signal-to-noise ratios, the recipe of the x-vector / ECAPA lineage (Kaldi's wav-reverberate).  Which clip, where
+in it and how loud are host decisions; only indices cross to the device.
 """
 from __future__ import annotations
 
@@ -234,6 +239,218 @@ def resample(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], orig_rate: 
     return out, out_lens
 
 
+MAX_NOISES = 8
+MAX_RIR_TAPS = 65536
+_LEVELS = ("input", "none")
+
+
+class SampleBank:
+    """Noise clips, or room impulse responses, as ONE packed float32 tensor on `device`.
+
+    `clips`: a sequence of 1-D float32 / int16 arrays or tensors (int16 is scaled by 1/32768), none empty.  Kept on the
+    host: `offsets` int64 [n + 1], `mean_square` float64 [n] (the mean of x^2 over the WHOLE clip, the noise power of
+    `augment`) and `delay` int64 [n] (the index of the first maximum of |x|: the direct sound of an impulse response).
+    Building the bank is the one place that synchronises: clips that live on a device are copied to the host for these
+    statistics."""
+
+    def __init__(self, clips, device="cuda"):
+        if isinstance(clips, (torch.Tensor, np.ndarray)) or len(clips) == 0:
+            raise ValueError("a SampleBank takes a non-empty sequence of 1-D clips")
+        host = []
+        for i, c in enumerate(clips):
+            a = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+            if a.ndim != 1 or a.dtype not in (np.float32, np.int16):
+                raise ValueError(f"clip {i} must be a 1-D float32 or int16 array, got {a.dtype} with {a.ndim} dimensions")
+            if a.size == 0:
+                raise ValueError(f"clip {i} is empty")
+            host.append(a.astype(np.float32) / np.float32(32768) if a.dtype == np.int16 else a)
+        self.offsets = np.concatenate([[0], np.cumsum([len(a) for a in host])]).astype(np.int64)
+        self.mean_square = np.array([np.mean(a.astype(np.float64) ** 2) for a in host], np.float64)
+        self.delay = np.array([int(np.argmax(np.abs(a))) for a in host], np.int64)
+        self.samples = torch.from_numpy(np.concatenate(host)).to(device)
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    @property
+    def lengths(self) -> np.ndarray:
+        return np.diff(self.offsets)
+
+    @property
+    def device(self) -> torch.device:
+        return self.samples.device
+
+
+@dataclass
+class AugmentPlan:
+    """What `augment` does to each utterance of a batch; all of it host data.
+
+    `rir_index` [n_utt]: the utterance's impulse response in `rir_bank`, -1 for none.  `noise_index`, `noise_start`,
+    `snr_db` [n_utt, J] (J <= MAX_NOISES): the clips of `noise_bank` added to the utterance (-1 for none), the sample of
+    the clip that meets the utterance's first, and the signal-to-noise ratio in dB.  `level`: "input" scales the result to
+    the input's power, "none" leaves it.  A plan without tables changes nothing."""
+    rir_bank: Optional[SampleBank] = None
+    rir_index: Optional[np.ndarray] = None
+    noise_bank: Optional[SampleBank] = None
+    noise_index: Optional[np.ndarray] = None
+    noise_start: Optional[np.ndarray] = None
+    snr_db: Optional[np.ndarray] = None
+    level: str = "input"
+
+
+def draw_augmentation(rs: np.random.RandomState, n_utt: int, rir_bank: Optional[SampleBank] = None,
+                      noise_bank: Optional[SampleBank] = None, p_rir: float = 0.5, p_noise: float = 0.5,
+                      snr_db: Tuple[float, float] = (0.0, 15.0), noises: Tuple[int, int] = (1, 1),
+                      level: str = "input") -> AugmentPlan:
+    """An `AugmentPlan` drawn from the caller's `rs`: with probability `p_rir` an utterance gets an impulse response drawn
+    uniformly from `rir_bank`; with probability `p_noise` it gets between noises[0] and noises[1] (inclusive) clips drawn
+    uniformly from `noise_bank`, each from a uniform start at a ratio uniform in snr_db = (lo, hi) dB.  The draws are made
+    in this order, whole arrays at a time: the reverberation coin and index, the noise coin, the count, then index,
+    start and ratio [n_utt, J]."""
+    if int(n_utt) != n_utt or n_utt < 1:
+        raise ValueError(f"n_utt must be a positive integer, got {n_utt!r}")
+    if not (0.0 <= p_rir <= 1.0 and 0.0 <= p_noise <= 1.0):
+        raise ValueError(f"p_rir and p_noise must be probabilities, got {p_rir!r}, {p_noise!r}")
+    lo, hi = (int(v) for v in noises)
+    if not 1 <= lo <= hi <= MAX_NOISES:
+        raise ValueError(f"noises must be (lo, hi) with 1 <= lo <= hi <= {MAX_NOISES}, got {noises!r}")
+    if not (math.isfinite(snr_db[0]) and math.isfinite(snr_db[1]) and snr_db[0] <= snr_db[1]):
+        raise ValueError(f"snr_db must be a finite (lo, hi), got {snr_db!r}")
+    n_utt = int(n_utt)
+    plan = AugmentPlan(level=level)
+    if rir_bank is not None:
+        coin = rs.random_sample(n_utt) < p_rir
+        plan.rir_bank = rir_bank
+        plan.rir_index = np.where(coin, rs.randint(0, len(rir_bank), n_utt), -1).astype(np.int64)
+    if noise_bank is not None:
+        coin = rs.random_sample(n_utt) < p_noise
+        count = np.where(coin, rs.randint(lo, hi + 1, n_utt), 0)
+        index = rs.randint(0, len(noise_bank), (n_utt, hi)).astype(np.int64)
+        start = np.floor(rs.random_sample((n_utt, hi)) * noise_bank.lengths[index]).astype(np.int64)
+        ratio = rs.uniform(snr_db[0], snr_db[1], (n_utt, hi))
+        used = np.arange(hi)[None, :] < count[:, None]
+        plan.noise_bank = noise_bank
+        plan.noise_index = np.where(used, index, -1)
+        plan.noise_start = np.where(used, start, 0)
+        plan.snr_db = np.where(used, ratio, 0.0)
+    return plan
+
+
+def _augment_tables(plan: AugmentPlan, n_utt: int, dev: torch.device):
+    """The validated host tables of a plan: (rir_tab [n_utt, 3] or None, largest K, noise_tab [n_utt, J, 5] or None)."""
+    if not isinstance(plan, AugmentPlan):
+        raise ValueError(f"augment takes an AugmentPlan, got {plan!r}")
+    if plan.level not in _LEVELS:
+        raise ValueError(f"level must be one of {_LEVELS}, got {plan.level!r}")
+
+    def bank_of(bank, what):
+        if not isinstance(bank, SampleBank):
+            raise ValueError(f"{what} needs a SampleBank, got {bank!r}")
+        if bank.device != dev:
+            raise ValueError(f"the {what} bank is on {bank.device}, the waveforms are on {dev}")
+        return bank
+
+    rir_tab, max_taps = None, 0
+    if plan.rir_index is not None:
+        bank = bank_of(plan.rir_bank, "rir_index")
+        idx = np.asarray(plan.rir_index)
+        if idx.shape != (n_utt,) or idx.dtype.kind not in "iu":
+            raise ValueError(f"rir_index must be {n_utt} integers, one per utterance, got shape {idx.shape} {idx.dtype}")
+        idx = idx.astype(np.int64)
+        if (idx < -1).any() or (idx >= len(bank)).any():
+            raise ValueError(f"rir_index must be -1 or an index into the bank's {len(bank)} impulse responses")
+        if (idx >= 0).any():
+            at = np.maximum(idx, 0)
+            rir_tab = np.stack([np.where(idx >= 0, bank.offsets[at], -1), bank.lengths[at], bank.delay[at]], 1)
+            max_taps = int(bank.lengths[idx[idx >= 0]].max())
+
+    noise_tab = None
+    given = [t is not None for t in (plan.noise_index, plan.noise_start, plan.snr_db)]
+    if any(given):
+        if not all(given):
+            raise ValueError("noise_index, noise_start and snr_db come together")
+        bank = bank_of(plan.noise_bank, "noise_index")
+        idx, start, snr = np.asarray(plan.noise_index), np.asarray(plan.noise_start), np.asarray(plan.snr_db, np.float64)
+        if idx.ndim != 2 or idx.shape[0] != n_utt or idx.shape[1] < 1 or start.shape != idx.shape or snr.shape != idx.shape:
+            raise ValueError(f"noise_index, noise_start and snr_db must share the shape [{n_utt}, J], got {idx.shape}, "
+                             f"{start.shape}, {snr.shape}")
+        if idx.shape[1] > MAX_NOISES:
+            raise ValueError(f"at most {MAX_NOISES} noises per utterance, got {idx.shape[1]}")
+        if idx.dtype.kind not in "iu" or start.dtype.kind not in "iu":
+            raise ValueError("noise_index and noise_start must be integers")
+        idx, start = idx.astype(np.int64), start.astype(np.int64)
+        if (idx < -1).any() or (idx >= len(bank)).any():
+            raise ValueError(f"noise_index must be -1 or an index into the bank's {len(bank)} clips")
+        on = idx >= 0
+        at = np.maximum(idx, 0)
+        if (on & ((start < 0) | (start >= bank.lengths[at]))).any():
+            raise ValueError("noise_start must lie inside its clip")
+        if not np.isfinite(snr[on]).all():
+            raise ValueError("snr_db must be finite")
+        if on.any():
+            if int(bank.lengths[at[on]].max()) >= 1 << 31:
+                raise ValueError("a noise clip must be shorter than 2^31 samples")
+            factor = 10.0 ** (np.where(on, snr, 0.0) / 10.0)
+            noise_tab = np.stack([np.where(on, bank.offsets[at], -1), bank.lengths[at], np.where(on, start, 0),
+                                  bank.mean_square[at].view(np.int64), factor.view(np.int64)], 2)
+    return rir_tab, max_taps, noise_tab
+
+
+def augment(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], plan: AugmentPlan,
+            lengths: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, np.ndarray]:
+    """The waveforms reverberated, mixed with noise and levelled as `plan` says, on the waveforms' device.
+
+    `waveforms` / `lengths`: as for `resample` (mono).  Utterance u with impulse response h of K taps (at most
+    MAX_RIR_TAPS) and delay p becomes r = np.convolve(x, h)[p : p + n]: the direct sound stays where it was and the length
+    does not change (Kaldi's wav-reverberate --shift-output=true).  Every noise clip v is then added from its start,
+    wrapping around, with the gain sqrt(P_r / (P_v * 10^(snr / 10))): P_r the mean square of the whole reverberated
+    utterance, P_v that of the whole clip.  With level="input" the sum is scaled to the input's mean square.  The powers
+    are accumulated in float64 on the device in a fixed order and every output sample is one fixed chain of fused
+    multiply-adds: the result does not depend on the batch.  Returns the packed 1-D float32 result and the host int64
+    lengths (unchanged); nothing is read back."""
+    eng = _eng()
+    packed, lens = _pack(waveforms, lengths)
+    dev = packed.device
+    n_utt = len(lens)
+    rir_tab, max_taps, noise_tab = _augment_tables(plan, n_utt, dev)
+
+    counts = np.zeros(4, np.int64)
+    lens_c = np.ascontiguousarray(lens)
+    tiling = lambda table: eng.lib.call("ds_augment_plan", lens_c.ctypes.data, n_utt,
+                                        None if table is None else table.ctypes.data, counts.ctypes.data)
+    tiling(None)
+    n_total, n_tiles = int(counts[0]), int(counts[1])
+    # one upload: the tile table, then the plan's tables (each at an even entry: 16-byte aligned)
+    n_plan = (2 * (n_utt + 1) + n_tiles + 1) & ~1
+    n_rir = 0 if rir_tab is None else (rir_tab.size + 1) & ~1
+    table = np.zeros(n_plan + n_rir + (0 if noise_tab is None else noise_tab.size), np.int64)
+    tiling(table)
+    if rir_tab is not None:
+        table[n_plan:n_plan + rir_tab.size] = rir_tab.reshape(-1)
+    if noise_tab is not None:
+        table[n_plan + n_rir:] = noise_tab.reshape(-1)
+    table_dev = _upload(table, dev)
+    rir_dev = None if rir_tab is None else table_dev[n_plan:]
+    noise_dev = None if noise_tab is None else table_dev[n_plan + n_rir:]
+
+    out = torch.empty(n_total, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(eng.lib.raw("ds_augment_workspace_bytes")(n_tiles)) // 8, dtype=torch.float64, device=dev)
+    stream = eng._stream(out)
+    eng.lib.call("ds_augment_reverb_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, eng._p(table_dev), n_utt,
+                 n_tiles, None if rir_tab is None else eng._p(plan.rir_bank.samples), eng._p(rir_dev), max_taps,
+                 eng._p(out), eng._p(ws), stream)
+    if noise_tab is not None:
+        eng.lib.call("ds_augment_mix_f32", eng._p(out), eng._p(table_dev), n_utt, n_tiles,
+                     eng._p(plan.noise_bank.samples), eng._p(noise_dev), noise_tab.shape[1], eng._p(ws), stream)
+    if plan.level == "input" and (rir_tab is not None or noise_tab is not None):
+        eng.lib.call("ds_augment_level_f32", eng._p(out), eng._p(table_dev), n_utt, n_tiles,
+                     1 if noise_tab is not None else 0, eng._p(ws), stream)
+    return out, lens.copy()
+
+
+_augment = augment                               # `augment=` is also a keyword of log_mel_fbank
+
+
 def _fbank_plan(eng, lens: np.ndarray, config: FbankConfig, dev: torch.device):
     """Framing on the host (the lengths are host data): (table on the device, frame offsets, frames, tiles, rows per
     tile) of ds_fbank_plan."""
@@ -409,8 +626,8 @@ def select_frames(feats: torch.Tensor, offsets: Sequence[int], mask: torch.Tenso
 
 def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config: FbankConfig = FbankConfig(),
                   normalize: Optional[str] = "mean", lengths: Optional[Sequence[int]] = None, *,
-                  orig_rate: Optional[int] = None, channels: int = 1, vad: Optional[VadConfig] = None
-                  ) -> Tuple[torch.Tensor, np.ndarray]:
+                  orig_rate: Optional[int] = None, channels: int = 1, vad: Optional[VadConfig] = None,
+                  augment: Optional[AugmentPlan] = None) -> Tuple[torch.Tensor, np.ndarray]:
     """mk_MFB of every waveform in one call chain on the waveforms' device.
 
     `waveforms`: a sequence of 1-D tensors (float32 samples, or int16 PCM, which is scaled by 1/32768), or ONE packed
@@ -422,6 +639,8 @@ def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config
     `vad`: given, only the voiced frames of `voiced_frames` (decided on the same, resampled, waveform) are kept, in
     order, and the normalisation runs over the kept rows; an utterance without a voiced frame has no row.  This reads the
     kept counts back (`select_frames`), so the call waits for the stream and cannot be captured into a graph.
+    `augment`: an `AugmentPlan`; the (resampled, mono) waveforms go through `augment` before the voice-activity decision
+    and the filterbank.
     Returns the packed [sum T_u, nfilt] float32 features on the device and the host int64 frame offsets [n_utt + 1]:
     utterance u is rows offsets[u]:offsets[u+1].  Decoding files is the caller's; deltas are not computed (the
     reference's USE_DELTA is False)."""
@@ -432,6 +651,8 @@ def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config
     if orig_rate is not None or channels != 1:
         waveforms, lengths = resample(waveforms, config.sample_rate if orig_rate is None else orig_rate,
                                       config.sample_rate, channels, lengths=lengths)
+    if augment is not None:
+        waveforms, lengths = _augment(waveforms, augment, lengths=lengths)
     eng = _eng()
     packed, lens = _pack(waveforms, lengths)
     dev = packed.device

@@ -94,7 +94,8 @@ int ds_version(void);            /* 100: round 1; 200: round 2 (fp16 path, group
                                     scheduler workspace); 700: log-mel filterbank front end (ds_fbank_*); 800: speaker identification
                                     (ds_nearest_*, ds_segment_mean_rows_f32, ds_rank_hits_i32); 900: polyphase resampler
                                     (ds_resample_plan, ds_resample_poly_f32); 1000: energy VAD (ds_vad_*); 1100: angular-margin softmax head;
-                                    1200: score normalisation (ds_cohort_*, ds_score_norm_apply_f32) */
+                                    1200: score normalisation (ds_cohort_*, ds_score_norm_apply_f32); 1300: waveform augmentation
+                                    (ds_augment_*) */
 /* launch timing without marker packets: the next MFMA convolution / filter-gradient launch of the calling thread
  * records its own execution into the armed pair (hipExtLaunchKernelGGL); ds_launch_timing_end() disarms and returns
  * how many such launches happened since arming (1 = the timed call was a single kernel) */
@@ -865,6 +866,42 @@ int ds_vad_scan(const unsigned char *mask, const long long *vtable, int n_utt, i
 int ds_vad_select_f32(const float *feat, const unsigned char *mask, const int *scan, const long long *vtable,
                       const long long *ktable, int n_utt, int n_ktiles, int nfilt, int tile_rows, float *out,
                       double *workspace, void *stream);
+
+/* ---- waveform augmentation (csrc/augment.hip): reverberation, additive noise at an SNR and the output level, on packed
+ * waveforms.  For utterance u of n samples x (int16 PCM scaled by 1/32768), an impulse response h of K taps with delay
+ * p (0 <= p < K) and up to 8 noise clips v_j with starts s_j:
+ *   r[m] = sum_k h[k] * x[m + p - k]   (0 <= m < n, 0 <= k < K, x zero outside [0, n): np.convolve(x, h)[p : p + n]);
+ *          r = x for an utterance without an impulse response
+ *   s[m] = r[m] + sum_j g_j * v_j[(s_j + m) mod len_j],  g_j = sqrt(P_r / (P_vj * 10^(snr_j / 10))), 0 when a power is 0
+ *   y    = s * sqrt(P_x / P_s)   (y = s when P_s = 0)
+ * P_x, P_r, P_s: mean squares over the utterance, accumulated in f64 in one fixed order; P_vj: the mean square of the
+ * whole clip, from the caller.  r is an f32 MFMA product of 32 x 32 Toeplitz blocks of h against the samples folded
+ * into columns of 32; every output is one fmaf chain fixed by its position in its utterance: deterministic, independent
+ * of tile, batch and call.  Every buffer is the caller's; nothing is allocated, read back or synchronised.
+ * ds_augment_plan (HOST): from the host sample counts `lengths[n_utt]`.  With table == NULL only counts[4] = {total
+ *   samples, tiles, outputs per tile, taps the reverberation kernel takes per pass} is written; otherwise also the int64
+ *   table off[n_utt+1] | tile_off[n_utt+1] | tile_utt[tiles] (2 * (n_utt + 1) + tiles entries), which the caller copies
+ *   to the device.  Tiles never straddle utterances.  An empty utterance is DS_ERR_BAD_SHAPE.
+ * ds_augment_workspace_bytes: the f64 workspace [tiles][3] = per-tile sums of x^2, r^2, s^2.
+ * ds_augment_reverb_f32: samples f32 (in_int16 = 0) or int16 (in_int16 = 1) -> out [total samples] f32 = r, and the
+ *   tiles' sums of x^2 and r^2 in the workspace.  rir_bank (device): the impulse responses, packed f32; rir_tab
+ *   (device): int64 [n_utt][3] = {offset of the utterance's h in rir_bank, or -1 for none; K; p}.  Both NULL: every
+ *   utterance is copied.  max_taps: the largest K of the call; above 65536 DS_ERR_UNSUPPORTED.
+ * ds_augment_mix_f32: data = r -> s in place, and the tiles' sums of s^2.  noise_tab (device): int64
+ *   [n_utt][n_noises][5] = {offset of the clip in noise_bank, or -1 for none; its length (< 2^31); s_j (0 <= s_j <
+ *   length); the bits of P_vj as f64; the bits of 10^(snr_j / 10) as f64}.  g_j is rounded to f32 once and s is one
+ *   fmaf chain over j.  n_noises > 8: DS_ERR_UNSUPPORTED.
+ * ds_augment_level_f32: data = s -> y in place; mixed = 1 after ds_augment_mix_f32, 0 straight after
+ *   ds_augment_reverb_f32 (s = r). */
+int ds_augment_plan(const long long *lengths, int n_utt, long long *table, long long *counts);
+long long ds_augment_workspace_bytes(int n_tiles);
+int ds_augment_reverb_f32(const void *samples, int in_int16, const long long *table, int n_utt, int n_tiles,
+                          const float *rir_bank, const long long *rir_tab, int max_taps, float *out, double *workspace,
+                          void *stream);
+int ds_augment_mix_f32(float *data, const long long *table, int n_utt, int n_tiles, const float *noise_bank,
+                       const long long *noise_tab, int n_noises, double *workspace, void *stream);
+int ds_augment_level_f32(float *data, const long long *table, int n_utt, int n_tiles, int mixed, const double *workspace,
+                         void *stream);
 
 #ifdef __cplusplus
 }
