@@ -25,6 +25,7 @@
 // Nothing is allocated, read back or synchronised.
 #include <ds_device.h>
 #include "ds_common.h"
+#include "ragged_tiles.h"
 
 namespace {
 
@@ -42,12 +43,6 @@ constexpr int AUG_HS = AUG_KCHUNK + 32;          // staged taps of one chunk (32
 constexpr int AUG_LDS_FLOATS = AUG_RED + AUG_HS + AUG_SPAN_COLS * AUG_XS;
 constexpr int AUG_WS = 3;                        // doubles per tile: sum x^2, sum r^2, sum s^2
 constexpr int AUG_NT = 5;                        // int64 entries per (utterance, noise)
-
-template <typename T> __device__ __forceinline__ float aug_sample(const T *x, long long i);
-template <> __device__ __forceinline__ float aug_sample<float>(const float *x, long long i) { return x[i]; }
-template <> __device__ __forceinline__ float aug_sample<short>(const short *x, long long i) {
-    return (float)x[i] * (1.0f / 32768.0f);
-}
 
 // the sum of v over the workgroup in one fixed order (butterfly inside a wave, then the waves in order), on every thread
 __device__ __forceinline__ double aug_block_sum(double v, double *red) {
@@ -68,17 +63,15 @@ __device__ __forceinline__ double aug_utt_sum(const double *ws, long long t0, lo
     return aug_block_sum(v, red);
 }
 
-// table (int64, device): off[n_utt+1] | tile_off[n_utt+1] | tile_utt[n_tiles]
+// table: ragged_table<1> of the samples, in tiles of AUG_TILE
 // rir_tab (int64, device): [n_utt][3] = {offset of h in the bank, or -1; K; p}
 template <typename T>
-__global__ void __launch_bounds__(AUG_THREADS) augment_reverb_kernel(const T *x, const long long *table, int n_utt,
-                                                                     const float *bank, const long long *rir_tab,
-                                                                     float *out, double *ws) {
-    const long long *off = table, *tile_off = table + n_utt + 1, *tile_utt = table + 2 * (n_utt + 1);
+__global__ void __launch_bounds__(AUG_THREADS) augment_reverb_kernel(const T *x, ragged_table<1> tb, const float *bank,
+                                                                     const long long *rir_tab, float *out, double *ws) {
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)tile_utt[tile];
-    const long long s0 = off[u], n = off[u + 1] - s0;
-    const long long m0 = (long long)(tile - tile_off[u]) * AUG_TILE;
+    const ragged_tile at = ragged_tile_of(tb, tile, AUG_TILE);
+    const int u = at.u;
+    const long long s0 = tb.col(0)[u], n = tb.count(0, u), m0 = at.first;
     const long long hoff = rir_tab ? rir_tab[3 * u] : -1;
     const bool filtered = hoff >= 0;
 
@@ -110,7 +103,7 @@ __global__ void __launch_bounds__(AUG_THREADS) augment_reverb_kernel(const T *x,
 #pragma unroll 4
             for (int s = t; s < 32 * AUG_SPAN_COLS; s += AUG_THREADS) {
                 const long long g = g0 + s;
-                xs[(s >> 5) * AUG_XS + (s & 31)] = (g >= 0 && g < n) ? aug_sample<T>(x, s0 + g) : 0.0f;
+                xs[(s >> 5) * AUG_XS + (s & 31)] = (g >= 0 && g < n) ? ds_pcm<T>(x, s0 + g) : 0.0f;
             }
             __syncthreads();
             // A[i][j] = hs[32 (DC - b) - 1 - i + j], B[j][a] = xs[(a - b + DC - 1) * 33 + j]; this lane's j = 2 jj + hi:
@@ -138,7 +131,7 @@ __global__ void __launch_bounds__(AUG_THREADS) augment_reverb_kernel(const T *x,
 #pragma unroll 4
     for (int m = t; m < AUG_TILE; m += AUG_THREADS) {
         if (m < left) {
-            const float xv = aug_sample<T>(x, s0 + m0 + m);
+            const float xv = ds_pcm<T>(x, s0 + m0 + m);
             const float rv = filtered ? xs[(m >> 5) * AUG_XS + (m & 31)] : xv;
             out[s0 + m0 + m] = rv;
             sx += (double)xv * (double)xv;
@@ -155,16 +148,14 @@ __global__ void __launch_bounds__(AUG_THREADS) augment_reverb_kernel(const T *x,
 
 // noise_tab (int64, device): [n_utt][J][5] = {offset of the clip in the bank, or -1; its length; the start in it;
 // bits of its mean square (f64); bits of 10^(snr / 10) (f64)}
-__global__ void __launch_bounds__(AUG_THREADS) augment_mix_kernel(float *data, const long long *table, int n_utt,
-                                                                  const float *bank, const long long *noise_tab, int J,
-                                                                  double *ws) {
-    const long long *off = table, *tile_off = table + n_utt + 1, *tile_utt = table + 2 * (n_utt + 1);
+__global__ void __launch_bounds__(AUG_THREADS) augment_mix_kernel(float *data, ragged_table<1> tb, const float *bank,
+                                                                  const long long *noise_tab, int J, double *ws) {
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)tile_utt[tile];
-    const long long s0 = off[u], n = off[u + 1] - s0;
-    const long long m0 = (long long)(tile - tile_off[u]) * AUG_TILE;
+    const ragged_tile at = ragged_tile_of(tb, tile, AUG_TILE);
+    const int u = at.u;
+    const long long s0 = tb.col(0)[u], n = tb.count(0, u), m0 = at.first;
     double *red = (double *)ds_dynamic_lds();
-    const double p_r = aug_utt_sum(ws, tile_off[u], tile_off[u + 1], 1, red) / (double)n;
+    const double p_r = aug_utt_sum(ws, tb.tile_off()[u], tb.tile_off()[u + 1], 1, red) / (double)n;
 
     float g[AUG_MAX_NOISES];
     const float *v[AUG_MAX_NOISES];
@@ -207,16 +198,15 @@ __global__ void __launch_bounds__(AUG_THREADS) augment_mix_kernel(float *data, c
     if (t == 0) ws[(long long)tile * AUG_WS + 2] = ss;
 }
 
-__global__ void __launch_bounds__(AUG_THREADS) augment_level_kernel(float *data, const long long *table, int n_utt,
-                                                                    int s_slot, const double *ws) {
-    const long long *off = table, *tile_off = table + n_utt + 1, *tile_utt = table + 2 * (n_utt + 1);
+__global__ void __launch_bounds__(AUG_THREADS) augment_level_kernel(float *data, ragged_table<1> tb, int s_slot,
+                                                                    const double *ws) {
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)tile_utt[tile];
-    const long long s0 = off[u], n = off[u + 1] - s0;
-    const long long m0 = (long long)(tile - tile_off[u]) * AUG_TILE;
+    const ragged_tile at = ragged_tile_of(tb, tile, AUG_TILE);
+    const int u = at.u;
+    const long long s0 = tb.col(0)[u], n = tb.count(0, u), m0 = at.first;
     double *red = (double *)ds_dynamic_lds();
-    const double sum_x = aug_utt_sum(ws, tile_off[u], tile_off[u + 1], 0, red);
-    const double sum_s = aug_utt_sum(ws, tile_off[u], tile_off[u + 1], s_slot, red);
+    const double sum_x = aug_utt_sum(ws, tb.tile_off()[u], tb.tile_off()[u + 1], 0, red);
+    const double sum_s = aug_utt_sum(ws, tb.tile_off()[u], tb.tile_off()[u + 1], s_slot, red);
     if (!(sum_s > 0.0)) return;                              // uniform over the workgroup: y = s
     const float scale = (float)sqrt(sum_x / sum_s);
     const long long left = n - m0;
@@ -229,26 +219,16 @@ __global__ void __launch_bounds__(AUG_THREADS) augment_level_kernel(float *data,
 extern "C" int ds_augment_plan(const long long *lengths, int n_utt, long long *table, long long *counts) {
     DS_REQUIRE(lengths && counts, DS_ERR_NULL);
     DS_REQUIRE(n_utt > 0, DS_ERR_BAD_SHAPE);
-    long long total = 0, tiles = 0;
+    ragged_plan<1> plan{table, n_utt};
     for (int u = 0; u < n_utt; ++u) {
         const long long len = lengths[u];
         DS_REQUIRE(len > 0 && len < (1LL << 40), DS_ERR_BAD_SHAPE);
-        const long long nt = (len + AUG_TILE - 1) / AUG_TILE;
-        if (table) {
-            table[u] = total;
-            table[n_utt + 1 + u] = tiles;
-            for (long long i = 0; i < nt; ++i) table[2 * (n_utt + 1) + tiles + i] = u;
-        }
-        total += len;
-        tiles += nt;
-        DS_REQUIRE(tiles < (1LL << 31) && total < (1LL << 44), DS_ERR_BAD_SHAPE);
+        plan.add(u, {len}, (len + AUG_TILE - 1) / AUG_TILE);
+        DS_REQUIRE(plan.tiles < (1LL << 31) && plan.total[0] < (1LL << 44), DS_ERR_BAD_SHAPE);
     }
-    if (table) {
-        table[n_utt] = total;
-        table[2 * n_utt + 1] = tiles;
-    }
-    counts[0] = total;
-    counts[1] = tiles;
+    plan.finish();
+    counts[0] = plan.total[0];
+    counts[1] = plan.tiles;
     counts[2] = AUG_TILE;
     counts[3] = AUG_KCHUNK;
     return 0;
@@ -268,11 +248,11 @@ extern "C" int ds_augment_reverb_f32(const void *samples, int in_int16, const lo
     DS_REQUIRE(max_taps <= AUG_MAX_TAPS, DS_ERR_UNSUPPORTED);
     const size_t lds = 4 * (size_t)AUG_LDS_FLOATS;
     if (in_int16)
-        DS_LAUNCH(augment_reverb_kernel<short>, n_tiles, AUG_THREADS, lds, stream, (const short *)samples, table, n_utt,
-                  rir_bank, rir_tab, out, workspace);
+        DS_LAUNCH(augment_reverb_kernel<short>, n_tiles, AUG_THREADS, lds, stream, (const short *)samples,
+                  ragged_table<1>{table, n_utt}, rir_bank, rir_tab, out, workspace);
     else
-        DS_LAUNCH(augment_reverb_kernel<float>, n_tiles, AUG_THREADS, lds, stream, (const float *)samples, table, n_utt,
-                  rir_bank, rir_tab, out, workspace);
+        DS_LAUNCH(augment_reverb_kernel<float>, n_tiles, AUG_THREADS, lds, stream, (const float *)samples,
+                  ragged_table<1>{table, n_utt}, rir_bank, rir_tab, out, workspace);
     return ds_last_launch_error();
 }
 
@@ -281,8 +261,8 @@ extern "C" int ds_augment_mix_f32(float *data, const long long *table, int n_utt
     DS_REQUIRE(data && table && noise_bank && noise_tab && workspace, DS_ERR_NULL);
     DS_REQUIRE(n_utt > 0 && n_tiles > 0 && n_noises > 0, DS_ERR_BAD_SHAPE);
     DS_REQUIRE(n_noises <= AUG_MAX_NOISES, DS_ERR_UNSUPPORTED);
-    DS_LAUNCH(augment_mix_kernel, n_tiles, AUG_THREADS, 4 * AUG_RED, stream, data, table, n_utt, noise_bank, noise_tab,
-              n_noises, workspace);
+    DS_LAUNCH(augment_mix_kernel, n_tiles, AUG_THREADS, 4 * AUG_RED, stream, data, ragged_table<1>{table, n_utt},
+              noise_bank, noise_tab, n_noises, workspace);
     return ds_last_launch_error();
 }
 
@@ -291,7 +271,7 @@ extern "C" int ds_augment_level_f32(float *data, const long long *table, int n_u
     DS_REQUIRE(data && table && workspace, DS_ERR_NULL);
     DS_REQUIRE(n_utt > 0 && n_tiles > 0, DS_ERR_BAD_SHAPE);
     DS_REQUIRE(mixed == 0 || mixed == 1, DS_ERR_UNSUPPORTED);
-    DS_LAUNCH(augment_level_kernel, n_tiles, AUG_THREADS, 4 * AUG_RED, stream, data, table, n_utt, mixed ? 2 : 1,
-              workspace);
+    DS_LAUNCH(augment_level_kernel, n_tiles, AUG_THREADS, 4 * AUG_RED, stream, data, ragged_table<1>{table, n_utt},
+              mixed ? 2 : 1, workspace);
     return ds_last_launch_error();
 }

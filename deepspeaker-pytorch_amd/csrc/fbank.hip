@@ -12,6 +12,7 @@
 //     deterministic and batch-invariant), then mean (and std) removed in place.
 #include <ds_device.h>
 #include "ds_common.h"
+#include "ragged_tiles.h"
 
 namespace {
 
@@ -43,26 +44,16 @@ __device__ __forceinline__ float fb_preemph(float x, float xm1) {
     return x - p;
 }
 
-template <typename T> __device__ __forceinline__ float fb_sample(const T *x, long long i);
-template <> __device__ __forceinline__ float fb_sample<float>(const float *x, long long i) { return x[i]; }
-template <> __device__ __forceinline__ float fb_sample<short>(const short *x, long long i) {
-    return (float)x[i] * (1.0f / 32768.0f);                  // exact in f32 (librosa's int16 scaling)
-}
-
-// table (int64, device): samp_off[n_utt+1] | frame_off[n_utt+1] | tile_off[n_utt+1] | tile_utt[n_tiles]
+// table: ragged_table<2> of (samples, frames), the frames in tiles
 template <typename T, int MB>
 __global__ void __launch_bounds__(FB_THREADS) fbank_logmel_kernel(
-    const T *x, const long long *table, int n_utt, const float *basis, const int *band, const float *mel_w, int wstride,
-    int frame_len, int frame_step, int nfft, int nfilt, int log_scale, float *out, double *partial) {
+    const T *x, ragged_table<2> tb, const float *basis, const int *band, const float *mel_w, int wstride, int frame_len,
+    int frame_step, int nfft, int nfilt, int log_scale, float *out, double *partial) {
     constexpr int TM = 32 * MB;
-    const long long *samp_off = table, *frame_off = table + n_utt + 1, *tile_off = table + 2 * (n_utt + 1);
-    const long long *tile_utt = table + 3 * (n_utt + 1);
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)tile_utt[tile];
-    const long long frame0 = (long long)(tile - (int)tile_off[u]) * TM;
-    const long long n_frames = frame_off[u + 1] - frame_off[u];
-    const int rows = (int)((n_frames - frame0) < TM ? (n_frames - frame0) : TM);
-    const long long s0 = samp_off[u], len = samp_off[u + 1] - s0;
+    const ragged_tile at = ragged_tile_of(tb, tile, TM);
+    const int u = at.u, rows = at.rows(tb.count(FB_FRAMES, u), TM);
+    const long long frame0 = at.first, s0 = tb.col(FB_SAMPLES)[u], len = tb.count(FB_SAMPLES, u);
     const int nb = nfft / 2 + 1, kpad = (frame_len + 1) & ~1, span = fb_span(TM, frame_len, frame_step);
 
     double *part = (double *)ds_dynamic_lds();               // [2][4][nfilt]
@@ -75,8 +66,8 @@ __global__ void __launch_bounds__(FB_THREADS) fbank_logmel_kernel(
         const long long g = g0 + s;
         float y = 0.0f;
         if (g < len) {
-            const float xg = fb_sample<T>(x, s0 + g);
-            y = g == 0 ? xg : fb_preemph(xg, fb_sample<T>(x, s0 + g - 1));
+            const float xg = ds_pcm<T>(x, s0 + g);
+            y = g == 0 ? xg : fb_preemph(xg, ds_pcm<T>(x, s0 + g - 1));
         }
         xs[s] = y;
     }
@@ -123,58 +114,35 @@ __global__ void __launch_bounds__(FB_THREADS) fbank_logmel_kernel(
     }
     __syncthreads();
 
-    // mel filterbank, floor, log; item (filter f, quarter q of the tile's rows)
-    const long long out_row0 = frame_off[u] + frame0;
-    constexpr int RQ = TM / 4;
-    for (int it = t; it < 4 * nfilt; it += FB_THREADS) {
-        const int f = it % nfilt, q = it / nfilt;
+    // mel filterbank, floor, log
+    ragged_tile_stats<FB_THREADS>(part, tile, rows, TM, nfilt, out + (tb.col(FB_FRAMES)[u] + frame0) * nfilt, partial,
+                                  [&](int f, int r) {
         const int b0 = band[2 * f], cnt = band[2 * f + 1];
-        const float *w = mel_w + (size_t)f * wstride;
-        double sum = 0.0, sq = 0.0;
-        for (int rr = 0; rr < RQ; ++rr) {
-            const int r = q * RQ + rr;
-            if (r >= rows) break;
-            const float *pr = pw + r * nb + b0;
-            double fb = 0.0;
-            for (int i = 0; i < cnt; ++i) fb += (double)w[i] * (double)pr[i];
-            if (fb == 0.0) fb = 2.220446049250313e-16;              // numpy.finfo(float).eps
-            const double v = log_scale ? 20.0 * log10(fb > 1e-5 ? fb : 1e-5) : fb;
-            // the statistics are those of the STORED values: x - mean is then exactly 0 where an utterance's frames
-            // are all equal (one frame, silence), as in the reference's float64 arithmetic
-            const float y = (float)v;
-            out[(out_row0 + r) * nfilt + f] = y;
-            sum += (double)y;
-            sq += (double)y * (double)y;
-        }
-        part[q * nfilt + f] = sum;
-        part[(4 + q) * nfilt + f] = sq;
-    }
-    __syncthreads();
-    for (int f = t; f < nfilt; f += FB_THREADS) {
-        double sum = 0.0, sq = 0.0;
-        for (int q = 0; q < 4; ++q) {
-            sum += part[q * nfilt + f];
-            sq += part[(4 + q) * nfilt + f];
-        }
-        partial[(size_t)tile * 2 * nfilt + f] = sum;
-        partial[(size_t)tile * 2 * nfilt + nfilt + f] = sq;
-    }
+        const float *w = mel_w + (size_t)f * wstride, *pr = pw + r * nb + b0;
+        double fb = 0.0;
+        for (int i = 0; i < cnt; ++i) fb += (double)w[i] * (double)pr[i];
+        if (fb == 0.0) fb = 2.220446049250313e-16;                      // numpy.finfo(float).eps
+        const double v = log_scale ? 20.0 * log10(fb > 1e-5 ? fb : 1e-5) : fb;
+        // the statistics are those of the STORED values: x - mean is then exactly 0 where an utterance's frames
+        // are all equal (one frame, silence), as in the reference's float64 arithmetic
+        return (float)v;
+    });
 }
 
 // per utterance: mean and (std + 2e-12) of every filter over its frames, from its tiles' partials in a fixed order
-__global__ void __launch_bounds__(FB_THREADS) fbank_stats_kernel(const long long *table, int n_utt, int nfilt,
+__global__ void __launch_bounds__(FB_THREADS) fbank_stats_kernel(ragged_table<2> tb, int nfilt,
                                                                  const double *partial, double *stats) {
-    const long long *frame_off = table + n_utt + 1, *tile_off = table + 2 * (n_utt + 1);
     double *lds = (double *)ds_dynamic_lds();                // [2][G][nfilt]
     const int u = blockIdx.x, t = threadIdx.x, G = FB_THREADS / nfilt;
-    const int t0 = (int)tile_off[u], nt = (int)(tile_off[u + 1] - t0), chunk = (nt + G - 1) / G;
+    const int t0 = (int)tb.tile_off()[u], nt = (int)(tb.tile_off()[u + 1] - t0), chunk = (nt + G - 1) / G;
     if (t < G * nfilt) {
         const int f = t % nfilt, g = t / nfilt;
         const int a = t0 + g * chunk, b = (t0 + (g + 1) * chunk) < (t0 + nt) ? t0 + (g + 1) * chunk : t0 + nt;
         double sum = 0.0, sq = 0.0;
         for (int i = a; i < b; ++i) {
-            sum += partial[(size_t)i * 2 * nfilt + f];
-            sq += partial[(size_t)i * 2 * nfilt + nfilt + f];
+            const double *of_tile = ragged_tile_stats_at(partial, i, nfilt);
+            sum += of_tile[f];
+            sq += of_tile[nfilt + f];
         }
         lds[g * nfilt + f] = sum;
         lds[(G + g) * nfilt + f] = sq;
@@ -186,7 +154,7 @@ __global__ void __launch_bounds__(FB_THREADS) fbank_stats_kernel(const long long
             sum += lds[g * nfilt + f];
             sq += lds[(G + g) * nfilt + f];
         }
-        const double n = (double)(frame_off[u + 1] - frame_off[u]);
+        const double n = (double)tb.count(FB_FRAMES, u);
         const double mean = sum / n, var = sq / n - mean * mean;
         stats[(size_t)u * 2 * nfilt + f] = mean;
         stats[(size_t)u * 2 * nfilt + nfilt + f] = sqrt(var > 0.0 ? var : 0.0) + 2e-12;
@@ -194,18 +162,16 @@ __global__ void __launch_bounds__(FB_THREADS) fbank_stats_kernel(const long long
 }
 
 // one workgroup per tile: x = (x - mean) [/ (std + 2e-12)], in place
-__global__ void __launch_bounds__(FB_THREADS) fbank_apply_kernel(float *feat, const long long *table, int n_utt,
+__global__ void __launch_bounds__(FB_THREADS) fbank_apply_kernel(float *feat, ragged_table<2> tb,
                                                                  int nfilt, int tm, int use_scale, const double *stats) {
-    const long long *frame_off = table + n_utt + 1, *tile_off = table + 2 * (n_utt + 1);
-    const long long *tile_utt = table + 3 * (n_utt + 1);
     double *st = (double *)ds_dynamic_lds();                 // [2][nfilt]
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)tile_utt[tile];
+    const ragged_tile at = ragged_tile_of(tb, tile, tm);
+    const int u = at.u;
     for (int i = t; i < 2 * nfilt; i += FB_THREADS) st[i] = stats[(size_t)u * 2 * nfilt + i];
     __syncthreads();
-    const long long frame0 = (long long)(tile - (int)tile_off[u]) * tm, n_frames = frame_off[u + 1] - frame_off[u];
-    const int rows = (int)((n_frames - frame0) < tm ? (n_frames - frame0) : tm);
-    float *y = feat + (frame_off[u] + frame0) * nfilt;
+    const int rows = at.rows(tb.count(FB_FRAMES, u), tm);
+    float *y = feat + (tb.col(FB_FRAMES)[u] + at.first) * nfilt;
     for (int e = t; e < rows * nfilt; e += FB_THREADS) {
         const int f = e % nfilt;
         double v = (double)y[e] - st[f];
@@ -218,21 +184,21 @@ __global__ void __launch_bounds__(FB_THREADS) fbank_apply_kernel(float *feat, co
 template <typename T>
 __global__ void __launch_bounds__(FB_THREADS) fbank_preemphasis_kernel(const T *x, long long n, float *y) {
     for (long long g = (long long)blockIdx.x * FB_THREADS + threadIdx.x; g < n; g += (long long)gridDim.x * FB_THREADS) {
-        const float xg = fb_sample<T>(x, g);
-        y[g] = g == 0 ? xg : fb_preemph(xg, fb_sample<T>(x, g - 1));
+        const float xg = ds_pcm<T>(x, g);
+        y[g] = g == 0 ? xg : fb_preemph(xg, ds_pcm<T>(x, g - 1));
     }
 }
 
 template <typename T>
-int fbank_launch(const T *x, const long long *table, int n_utt, int n_tiles, int tm, const float *basis, const int *band,
+int fbank_launch(const T *x, ragged_table<2> tb, int n_tiles, int tm, const float *basis, const int *band,
                  const float *mel_w, int wstride, int frame_len, int frame_step, int nfft, int nfilt, int log_scale,
                  float *out, double *partial, void *stream) {
     const size_t lds = (size_t)fb_lds_bytes(tm, frame_len, frame_step, nfft, nfilt);
     if (tm == 64)
-        DS_LAUNCH_BIG_LDS((fbank_logmel_kernel<T, 2>), n_tiles, FB_THREADS, lds, stream, x, table, n_utt, basis, band,
+        DS_LAUNCH_BIG_LDS((fbank_logmel_kernel<T, 2>), n_tiles, FB_THREADS, lds, stream, x, tb, basis, band,
                           mel_w, wstride, frame_len, frame_step, nfft, nfilt, log_scale, out, partial);
     else
-        DS_LAUNCH_BIG_LDS((fbank_logmel_kernel<T, 1>), n_tiles, FB_THREADS, lds, stream, x, table, n_utt, basis, band,
+        DS_LAUNCH_BIG_LDS((fbank_logmel_kernel<T, 1>), n_tiles, FB_THREADS, lds, stream, x, tb, basis, band,
                           mel_w, wstride, frame_len, frame_step, nfft, nfilt, log_scale, out, partial);
     return ds_last_launch_error();
 }
@@ -245,31 +211,19 @@ extern "C" int ds_fbank_plan(const long long *lengths, int n_utt, int frame_len,
     DS_REQUIRE(n_utt > 0, DS_ERR_BAD_SHAPE);
     const int tm = fb_tile_rows(frame_len, frame_step, nfft, nfilt);
     DS_REQUIRE(tm > 0, DS_ERR_UNSUPPORTED);
-    long long samples = 0, frames = 0, tiles = 0;
+    ragged_plan<2> plan{table, n_utt};
     for (int u = 0; u < n_utt; ++u) {
         const long long len = lengths[u];
         DS_REQUIRE(len > 0, DS_ERR_BAD_SHAPE);                // an empty signal has no frame (the reference fails too)
         // python_speech_features.sigproc.framesig: one frame up to frame_len samples, then one per started step
         const long long nf = len <= frame_len ? 1 : 1 + (len - frame_len + frame_step - 1) / frame_step;
-        const long long nt = (nf + tm - 1) / tm;
-        if (table) {
-            table[u] = samples;
-            table[n_utt + 1 + u] = frames;
-            table[2 * (n_utt + 1) + u] = tiles;
-            for (long long i = 0; i < nt; ++i) table[3 * (n_utt + 1) + tiles + i] = u;
-        }
-        samples += len;
-        frames += nf;
-        tiles += nt;
+        plan.add(u, {len, nf}, (nf + tm - 1) / tm);
     }
-    DS_REQUIRE(tiles < (1LL << 31) && frames * nfilt < (1LL << 40), DS_ERR_BAD_SHAPE);
-    if (table) {
-        table[n_utt] = samples;
-        table[2 * n_utt + 1] = frames;
-        table[3 * n_utt + 2] = tiles;
-    }
+    const long long frames = plan.total[FB_FRAMES];
+    DS_REQUIRE(plan.tiles < (1LL << 31) && frames * nfilt < (1LL << 40), DS_ERR_BAD_SHAPE);
+    plan.finish();
     counts[0] = frames;
-    counts[1] = tiles;
+    counts[1] = plan.tiles;
     counts[2] = tm;
     return 0;
 }
@@ -289,9 +243,9 @@ extern "C" int ds_fbank_logmel_f32(const void *samples, int in_int16, const long
     const int tm = fb_tile_rows(frame_len, frame_step, nfft, nfilt);
     DS_REQUIRE(tm > 0, DS_ERR_UNSUPPORTED);
     if (in_int16)
-        return fbank_launch((const short *)samples, table, n_utt, n_tiles, tm, basis, band, mel_w, wstride, frame_len,
+        return fbank_launch((const short *)samples, {table, n_utt}, n_tiles, tm, basis, band, mel_w, wstride, frame_len,
                             frame_step, nfft, nfilt, log_scale, out, workspace, stream);
-    return fbank_launch((const float *)samples, table, n_utt, n_tiles, tm, basis, band, mel_w, wstride, frame_len,
+    return fbank_launch((const float *)samples, {table, n_utt}, n_tiles, tm, basis, band, mel_w, wstride, frame_len,
                         frame_step, nfft, nfilt, log_scale, out, workspace, stream);
 }
 
@@ -300,12 +254,13 @@ extern "C" int ds_fbank_normalize_f32(float *feat, const long long *table, int n
     DS_REQUIRE(feat && table && workspace, DS_ERR_NULL);
     DS_REQUIRE(n_utt > 0 && n_tiles > 0 && (tile_rows == 64 || tile_rows == 32), DS_ERR_BAD_SHAPE);
     DS_REQUIRE(nfilt >= 4 && nfilt <= 128 && (nfilt & 3) == 0, DS_ERR_UNSUPPORTED);
+    const ragged_table<2> tb{table, n_utt};
     const double *partial = workspace;
     double *stats = workspace + (size_t)n_tiles * 2 * nfilt;
-    DS_LAUNCH(fbank_stats_kernel, n_utt, FB_THREADS, 2 * FB_THREADS * 8, stream, table, n_utt, nfilt, partial, stats);
+    DS_LAUNCH(fbank_stats_kernel, n_utt, FB_THREADS, 2 * FB_THREADS * 8, stream, tb, nfilt, partial, stats);
     const int rc = ds_last_launch_error();
     if (rc) return rc;
-    DS_LAUNCH(fbank_apply_kernel, n_tiles, FB_THREADS, 2 * nfilt * 8, stream, feat, table, n_utt, nfilt, tile_rows,
+    DS_LAUNCH(fbank_apply_kernel, n_tiles, FB_THREADS, 2 * nfilt * 8, stream, feat, tb, nfilt, tile_rows,
               use_scale != 0, (const double *)stats);
     return ds_last_launch_error();
 }

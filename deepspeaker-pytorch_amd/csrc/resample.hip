@@ -15,6 +15,7 @@
 //     (as a Toeplitz product on the MFMA, L = 1 has one useful column and 160/441 is ~9x zero work).
 #include <ds_device.h>
 #include "ds_common.h"
+#include "ragged_tiles.h"
 
 namespace {
 
@@ -50,32 +51,26 @@ inline bool rs_geometry(int L, int M, int H, rs_geom *g) {
     return false;
 }
 
-template <typename T> __device__ __forceinline__ float rs_sample(const T *x, long long i);
-template <> __device__ __forceinline__ float rs_sample<float>(const float *x, long long i) { return x[i]; }
-template <> __device__ __forceinline__ float rs_sample<short>(const short *x, long long i) {
-    return (float)x[i] * (1.0f / 32768.0f);                  // exact in f32 (librosa's int16 scaling)
-}
-
 // frame f of interleaved [n][C] samples as mono: channels summed in order in f32, then divided by C in f32
 template <typename T>
 __device__ __forceinline__ float rs_mono(const T *x, long long f, int C) {
-    if (C == 1) return rs_sample<T>(x, f);
-    float s = rs_sample<T>(x, f * C);
-    for (int c = 1; c < C; ++c) s += rs_sample<T>(x, f * C + c);
+    if (C == 1) return ds_pcm<T>(x, f);
+    float s = ds_pcm<T>(x, f * C);
+    for (int c = 1; c < C; ++c) s += ds_pcm<T>(x, f * C + c);
     return s / (float)C;
 }
 
-// table (int64, device): in_off[n_utt+1] | out_off[n_utt+1] | tile_off[n_utt+1] | tile_utt[n_tiles]
+// table: ragged_table<2> of (input frames, outputs), the outputs in tiles
+constexpr int RS_IN = 0, RS_OUT = 1;
+
 template <typename T>
-__global__ void __launch_bounds__(RS_THREADS) resample_poly_kernel(const T *x, int C, const long long *table, int n_utt,
+__global__ void __launch_bounds__(RS_THREADS) resample_poly_kernel(const T *x, int C, ragged_table<2> tb,
                                                                    const float *taps, rs_geom g, float *out) {
-    const long long *in_off = table, *out_off = table + n_utt + 1, *tile_off = table + 2 * (n_utt + 1);
-    const long long *tile_utt = table + 3 * (n_utt + 1);
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)tile_utt[tile];
-    const long long s0 = in_off[u], n = in_off[u + 1] - s0;
-    const long long o0 = out_off[u], n_out = out_off[u + 1] - o0;
-    const long long m0 = (long long)(tile - (int)tile_off[u]) * RS_R * g.S;
+    const ragged_tile at = ragged_tile_of(tb, tile, RS_R * g.S);
+    const int u = at.u;
+    const long long s0 = tb.col(RS_IN)[u], n = tb.count(RS_IN, u);
+    const long long o0 = tb.col(RS_OUT)[u], n_out = tb.count(RS_OUT, u), m0 = at.first;
     // output m0 + e reads inputs k0 + (pc + e*M) / L + [0, T) with the taps of phase (pc + e*M) % L
     const long long c0 = (long long)g.H + m0 * g.M;
     const long long k0 = c0 / g.L - g.T + 1;
@@ -122,30 +117,18 @@ extern "C" int ds_resample_plan(const long long *lengths, int n_utt, int up, int
     rs_geom g;
     DS_REQUIRE(rs_geometry(up, down, half_width, &g), DS_ERR_UNSUPPORTED);
     const long long tile_out = (long long)RS_R * g.S;
-    long long in = 0, outs = 0, tiles = 0;
+    ragged_plan<2> plan{table, n_utt};
     for (int u = 0; u < n_utt; ++u) {
         const long long len = lengths[u];
         DS_REQUIRE(len > 0 && len < (1LL << 40), DS_ERR_BAD_SHAPE);
         const long long no = (len * up + down - 1) / down;
-        const long long nt = (no + tile_out - 1) / tile_out;
-        if (table) {
-            table[u] = in;
-            table[n_utt + 1 + u] = outs;
-            table[2 * (n_utt + 1) + u] = tiles;
-            for (long long i = 0; i < nt; ++i) table[3 * (n_utt + 1) + tiles + i] = u;
-        }
-        in += len;
-        outs += no;
-        tiles += nt;
-        DS_REQUIRE(tiles < (1LL << 31) && in < (1LL << 44) && outs < (1LL << 44), DS_ERR_BAD_SHAPE);
+        plan.add(u, {len, no}, (no + tile_out - 1) / tile_out);
+        DS_REQUIRE(plan.tiles < (1LL << 31) && plan.total[RS_IN] < (1LL << 44) && plan.total[RS_OUT] < (1LL << 44),
+                   DS_ERR_BAD_SHAPE);
     }
-    if (table) {
-        table[n_utt] = in;
-        table[2 * n_utt + 1] = outs;
-        table[3 * n_utt + 2] = tiles;
-    }
-    counts[0] = outs;
-    counts[1] = tiles;
+    plan.finish();
+    counts[0] = plan.total[RS_OUT];
+    counts[1] = plan.tiles;
     counts[2] = tile_out;
     return 0;
 }
@@ -162,9 +145,9 @@ extern "C" int ds_resample_poly_f32(const void *samples, int in_int16, int chann
     const size_t lds = 4 * ((size_t)g.L * g.TP + (size_t)g.span);
     if (in_int16)
         DS_LAUNCH_BIG_LDS(resample_poly_kernel<short>, n_tiles, RS_THREADS, lds, stream, (const short *)samples, channels,
-                          table, n_utt, taps, g, out);
+                          ragged_table<2>{table, n_utt}, taps, g, out);
     else
         DS_LAUNCH_BIG_LDS(resample_poly_kernel<float>, n_tiles, RS_THREADS, lds, stream, (const float *)samples, channels,
-                          table, n_utt, taps, g, out);
+                          ragged_table<2>{table, n_utt}, taps, g, out);
     return ds_last_launch_error();
 }

@@ -3,11 +3,11 @@
 //   e[t]   = ln(max(sum_i (32768 x[t*step + i])^2, floor)),  0 <= i < frame_len, samples past the end are zero
 //   thr    = energy_threshold + energy_mean_scale * mean_t e[t]                       (f64, fixed order)
 //   voiced = count(e[lo..hi] > thr) >= proportion * (hi - lo + 1),  lo = max(0, t - ctx), hi = min(T - 1, t + ctx)
-//   * vad_energy_kernel: one workgroup per tile of the FBANK table (fbank.hip: samp_off | frame_off | tile_off |
-//     tile_utt).  The tile's sample span is staged into LDS once, on the int16 scale; a wavefront sums one frame: lane l
+//   * vad_energy_kernel: one workgroup per tile of the FBANK table (ds_fbank_plan: samples and frames, the frames in
+//     tiles).  The tile's sample span is staged into LDS once, on the int16 scale; a wavefront sums one frame: lane l
 //     takes samples l, l + 64, ... in order (consecutive LDS words: no bank conflict), then a fixed xor butterfly.  The
 //     order depends on nothing but the sample's place in its frame: deterministic, independent of tile, batch and call.
-//   * the decision works on tiles of VAD_DT frames of one utterance (ds_vad_plan: frame_off | dtile_off | dtile_utt):
+//   * the decision works on tiles of VAD_DT frames of one utterance (ds_vad_plan: the frames alone):
 //       vad_threshold_kernel  one workgroup per utterance: the f64 mean in a fixed order (no atomics), the threshold
 //       vad_vote_kernel       one workgroup per tile: e > thr of the tile and its halo in LDS, the clipped-window vote,
 //                             the uint8 mask and the tile's kept count
@@ -20,6 +20,7 @@
 //     layout and order, so ds_fbank_normalize_f32 normalises the kept rows with the table over them.
 #include <ds_device.h>
 #include "ds_common.h"
+#include "ragged_tiles.h"
 #include <math.h>
 
 namespace {
@@ -32,24 +33,16 @@ constexpr int VAD_LDS_MAX = 160 * 1024;
 
 inline long long vad_span(int tm, int frame_len, int frame_step) { return (long long)(tm - 1) * frame_step + frame_len; }
 
-// samples on the int16 scale: the integer itself, or the float times 32768 (a power of two: exact)
-template <typename T> __device__ __forceinline__ float vad_sample(const T *x, long long i);
-template <> __device__ __forceinline__ float vad_sample<float>(const float *x, long long i) { return x[i] * 32768.0f; }
-template <> __device__ __forceinline__ float vad_sample<short>(const short *x, long long i) { return (float)x[i]; }
-
-// table (int64, device): samp_off[n_utt+1] | frame_off[n_utt+1] | tile_off[n_utt+1] | tile_utt[n_tiles]  (ds_fbank_plan)
+// table: ds_fbank_plan's, ragged_table<2> of (samples, frames), the frames in tiles of tm; the samples enter on the
+// int16 scale
 template <typename T>
-__global__ void __launch_bounds__(VAD_THREADS) vad_energy_kernel(const T *x, const long long *table, int n_utt, int tm,
+__global__ void __launch_bounds__(VAD_THREADS) vad_energy_kernel(const T *x, ragged_table<2> tb, int tm,
                                                                  int frame_len, int frame_step, float floor_v,
                                                                  float log_floor, float *out) {
-    const long long *samp_off = table, *frame_off = table + n_utt + 1, *tile_off = table + 2 * (n_utt + 1);
-    const long long *tile_utt = table + 3 * (n_utt + 1);
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)tile_utt[tile];
-    const long long frame0 = (long long)(tile - (int)tile_off[u]) * tm;
-    const long long n_frames = frame_off[u + 1] - frame_off[u];
-    const int rows = (int)((n_frames - frame0) < tm ? (n_frames - frame0) : tm);
-    const long long s0 = samp_off[u], len = samp_off[u + 1] - s0;
+    const ragged_tile at = ragged_tile_of(tb, tile, tm);
+    const int u = at.u, rows = at.rows(tb.count(FB_FRAMES, u), tm);
+    const long long frame0 = at.first, s0 = tb.col(FB_SAMPLES)[u], len = tb.count(FB_SAMPLES, u);
     const int span = (rows - 1) * frame_step + frame_len;
 
     float *es = ds_dynamic_lds();                            // [tm] frame sums
@@ -57,7 +50,7 @@ __global__ void __launch_bounds__(VAD_THREADS) vad_energy_kernel(const T *x, con
     const long long g0 = frame0 * frame_step;
     for (int s = t; s < span; s += VAD_THREADS) {
         const long long g = g0 + s;
-        xs[s] = g < len ? vad_sample<T>(x, s0 + g) : 0.0f;
+        xs[s] = g < len ? ds_pcm_i16<T>(x, s0 + g) : 0.0f;
     }
     __syncthreads();
 
@@ -73,17 +66,17 @@ __global__ void __launch_bounds__(VAD_THREADS) vad_energy_kernel(const T *x, con
     __syncthreads();
     for (int r = t; r < rows; r += VAD_THREADS) {
         const float s = es[r];
-        out[frame_off[u] + frame0 + r] = s > floor_v ? logf(s) : log_floor;
+        out[tb.col(FB_FRAMES)[u] + frame0 + r] = s > floor_v ? logf(s) : log_floor;
     }
 }
 
-// vtable (int64, device): frame_off[n_utt+1] | dtile_off[n_utt+1] | dtile_utt[n_dtiles]  (ds_vad_plan)
-__global__ void __launch_bounds__(VAD_THREADS) vad_threshold_kernel(const float *energy, const long long *vtable,
-                                                                    double energy_threshold, double energy_mean_scale,
-                                                                    double *thr) {
+// vtable: ds_vad_plan's, ragged_table<1> of the frames, in tiles of VAD_DT
+__global__ void __launch_bounds__(VAD_THREADS) vad_threshold_kernel(const float *energy, ragged_table<1> vt,
+                                                                    double energy_threshold,
+                                                                    double energy_mean_scale, double *thr) {
     double *lds = (double *)ds_dynamic_lds();                // [VAD_THREADS]
     const int u = blockIdx.x, t = threadIdx.x;
-    const long long f0 = vtable[u], T = vtable[u + 1] - f0;
+    const long long f0 = vt.col(0)[u], T = vt.count(0, u);
     double s = 0.0;
     for (long long i = t; i < T; i += VAD_THREADS) s += (double)energy[f0 + i];
     lds[t] = s;
@@ -108,17 +101,16 @@ __device__ __forceinline__ int vad_block_sum(int *lds, int t, int mine) {
     return total;
 }
 
-__global__ void __launch_bounds__(VAD_THREADS) vad_vote_kernel(const float *energy, const long long *vtable, int n_utt,
+__global__ void __launch_bounds__(VAD_THREADS) vad_vote_kernel(const float *energy, ragged_table<1> vt,
                                                                const double *thr, int ctx, double proportion,
                                                                unsigned char *mask, long long *tile_count) {
-    const long long *frame_off = vtable, *dtile_off = vtable + n_utt + 1, *dtile_utt = vtable + 2 * (n_utt + 1);
     int *red = (int *)ds_dynamic_lds();                      // [VAD_THREADS]
     unsigned char *above = (unsigned char *)(red + VAD_THREADS);   // [VAD_DT + 2 ctx]: frames first - ctx ...
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)dtile_utt[tile];
-    const long long f0 = frame_off[u], T = frame_off[u + 1] - f0;
-    const long long first = (tile - dtile_off[u]) * VAD_DT;
-    const int rows = (int)((T - first) < VAD_DT ? (T - first) : VAD_DT);
+    const ragged_tile at = ragged_tile_of(vt, tile, VAD_DT);
+    const int u = at.u;
+    const long long f0 = vt.col(0)[u], T = vt.count(0, u), first = at.first;
+    const int rows = at.rows(T, VAD_DT);
     const double th = thr[u];
     for (int i = t; i < rows + 2 * ctx; i += VAD_THREADS) {
         const long long f = first - ctx + i;                 // never a neighbouring utterance's frame
@@ -140,15 +132,13 @@ __global__ void __launch_bounds__(VAD_THREADS) vad_vote_kernel(const float *ener
 }
 
 // a caller's own mask: the tile's count of non-zero entries
-__global__ void __launch_bounds__(VAD_THREADS) vad_count_kernel(const unsigned char *mask, const long long *vtable,
-                                                                int n_utt, long long *tile_count) {
-    const long long *frame_off = vtable, *dtile_off = vtable + n_utt + 1, *dtile_utt = vtable + 2 * (n_utt + 1);
+__global__ void __launch_bounds__(VAD_THREADS) vad_count_kernel(const unsigned char *mask, ragged_table<1> vt,
+                                                                long long *tile_count) {
     int *red = (int *)ds_dynamic_lds();
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)dtile_utt[tile];
-    const long long f0 = frame_off[u], T = frame_off[u + 1] - f0;
-    const long long first = (tile - dtile_off[u]) * VAD_DT;
-    const int rows = (int)((T - first) < VAD_DT ? (T - first) : VAD_DT);
+    const ragged_tile at = ragged_tile_of(vt, tile, VAD_DT);
+    const long long f0 = vt.col(0)[at.u], first = at.first;
+    const int rows = at.rows(vt.count(0, at.u), VAD_DT);
     int kept = 0;
     for (int r = t; r < rows; r += VAD_THREADS) kept += mask[f0 + first + r] != 0;
     const int total = vad_block_sum(red, t, kept);
@@ -157,12 +147,11 @@ __global__ void __launch_bounds__(VAD_THREADS) vad_count_kernel(const unsigned c
 
 // per utterance: its tiles' counts -> their exclusive scan (in place), and the kept count.  Thread t owns a contiguous
 // run of tiles; the runs' totals are scanned by one thread (256 additions)
-__global__ void __launch_bounds__(VAD_THREADS) vad_tile_scan_kernel(const long long *vtable, int n_utt,
+__global__ void __launch_bounds__(VAD_THREADS) vad_tile_scan_kernel(ragged_table<1> vt,
                                                                     long long *tile_count, long long *kept) {
-    const long long *dtile_off = vtable + n_utt + 1;
     long long *lds = (long long *)ds_dynamic_lds();          // [VAD_THREADS + 1]
     const int u = blockIdx.x, t = threadIdx.x;
-    const long long t0 = dtile_off[u], nt = dtile_off[u + 1] - t0, run = (nt + VAD_THREADS - 1) / VAD_THREADS;
+    const long long t0 = vt.tile_off()[u], nt = vt.tile_off()[u + 1] - t0, run = (nt + VAD_THREADS - 1) / VAD_THREADS;
     const long long a = t0 + t * run < t0 + nt ? t0 + t * run : t0 + nt;
     const long long b = a + run < t0 + nt ? a + run : t0 + nt;
     long long s = 0;
@@ -189,15 +178,13 @@ __global__ void __launch_bounds__(VAD_THREADS) vad_tile_scan_kernel(const long l
 }
 
 // scan[f] = kept frames of the utterance before f.  Thread t owns VAD_PER consecutive frames of the tile
-__global__ void __launch_bounds__(VAD_THREADS) vad_scan_kernel(const unsigned char *mask, const long long *vtable,
-                                                               int n_utt, const long long *tile_base, int *scan) {
-    const long long *frame_off = vtable, *dtile_off = vtable + n_utt + 1, *dtile_utt = vtable + 2 * (n_utt + 1);
+__global__ void __launch_bounds__(VAD_THREADS) vad_scan_kernel(const unsigned char *mask, ragged_table<1> vt,
+                                                               const long long *tile_base, int *scan) {
     int *lds = (int *)ds_dynamic_lds();                      // [2][VAD_THREADS]
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)dtile_utt[tile];
-    const long long f0 = frame_off[u], T = frame_off[u + 1] - f0;
-    const long long first = (tile - dtile_off[u]) * VAD_DT;
-    const int rows = (int)((T - first) < VAD_DT ? (T - first) : VAD_DT);
+    const ragged_tile at = ragged_tile_of(vt, tile, VAD_DT);
+    const long long f0 = vt.col(0)[at.u], first = at.first;
+    const int rows = at.rows(vt.count(0, at.u), VAD_DT);
     const unsigned char *m = mask + f0 + first;
     int v[VAD_PER], mine = 0;
 #pragma unroll
@@ -227,20 +214,16 @@ __global__ void __launch_bounds__(VAD_THREADS) vad_scan_kernel(const unsigned ch
     }
 }
 
-// ktable (int64, device): the fbank table's layout over the KEPT frames (its samp_off part is not read)
+// ktable: ragged_table<2> as ds_fbank_plan's over the KEPT frames, in tiles of tm (its samples column is not read)
 __global__ void __launch_bounds__(VAD_THREADS) vad_select_kernel(const float *feat, const unsigned char *mask,
-                                                                 const int *scan, const long long *vtable,
-                                                                 const long long *ktable, int n_utt, int nfilt, int tm,
-                                                                 float *out, double *partial) {
-    const long long *kframe_off = ktable + n_utt + 1, *ktile_off = ktable + 2 * (n_utt + 1);
-    const long long *ktile_utt = ktable + 3 * (n_utt + 1);
+                                                                 const int *scan, ragged_table<1> vt, ragged_table<2> kt,
+                                                                 int nfilt, int tm, float *out, double *partial) {
     double *part = (double *)ds_dynamic_lds();               // [2][4][nfilt]
     long long *src_row = (long long *)(part + 8 * nfilt);    // [tm]
     const int tile = blockIdx.x, t = threadIdx.x;
-    const int u = (int)ktile_utt[tile];
-    const long long k0 = (long long)(tile - (int)ktile_off[u]) * tm, K = kframe_off[u + 1] - kframe_off[u];
-    const int rows = (int)((K - k0) < tm ? (K - k0) : tm);
-    const long long f0 = vtable[u], T = vtable[u + 1] - f0;
+    const ragged_tile at = ragged_tile_of(kt, tile, tm);
+    const int u = at.u, rows = at.rows(kt.count(FB_FRAMES, u), tm);
+    const long long k0 = at.first, f0 = vt.col(0)[u], T = vt.count(0, u);
 
     // output row k is the LAST frame j with scan[j] <= k (the scan steps up right after every kept frame)
     for (int r = t; r < rows; r += VAD_THREADS) {
@@ -254,43 +237,21 @@ __global__ void __launch_bounds__(VAD_THREADS) vad_select_kernel(const float *fe
     }
     __syncthreads();
 
-    // copy and statistics; item (filter f, quarter q of the tile's rows), as in fbank_logmel_kernel's epilogue
-    float *dst = out + (kframe_off[u] + k0) * nfilt;
-    const int RQ = tm / 4;
-    for (int it = t; it < 4 * nfilt; it += VAD_THREADS) {
-        const int f = it % nfilt, q = it / nfilt;
-        double sum = 0.0, sq = 0.0;
-        for (int rr = 0; rr < RQ; ++rr) {
-            const int r = q * RQ + rr;
-            if (r >= rows) break;
-            const long long j = src_row[r];
-            const float y = j >= 0 ? feat[j * nfilt + f] : 0.0f;     // j < 0: scan and table disagree (not the library's)
-            dst[(long long)r * nfilt + f] = y;
-            sum += (double)y;
-            sq += (double)y * (double)y;
-        }
-        part[q * nfilt + f] = sum;
-        part[(4 + q) * nfilt + f] = sq;
-    }
-    __syncthreads();
-    for (int f = t; f < nfilt; f += VAD_THREADS) {
-        double sum = 0.0, sq = 0.0;
-        for (int q = 0; q < 4; ++q) {
-            sum += part[q * nfilt + f];
-            sq += part[(4 + q) * nfilt + f];
-        }
-        partial[(size_t)tile * 2 * nfilt + f] = sum;
-        partial[(size_t)tile * 2 * nfilt + nfilt + f] = sq;
-    }
+    // copy and statistics
+    ragged_tile_stats<VAD_THREADS>(part, tile, rows, tm, nfilt, out + (kt.col(FB_FRAMES)[u] + k0) * nfilt, partial,
+                                   [&](int f, int r) {
+        const long long j = src_row[r];
+        return j >= 0 ? feat[j * nfilt + f] : 0.0f;                  // j < 0: scan and table disagree (not the library's)
+    });
 }
 
 // the scan half of the decision: tile counts (already written) -> scan and kept
-int vad_scan_launch(const unsigned char *mask, const long long *vtable, int n_utt, int n_dtiles, long long *tile_count,
+int vad_scan_launch(const unsigned char *mask, ragged_table<1> vt, int n_dtiles, long long *tile_count,
                     int *scan, long long *kept, void *stream) {
-    DS_LAUNCH(vad_tile_scan_kernel, n_utt, VAD_THREADS, (VAD_THREADS + 1) * 8, stream, vtable, n_utt, tile_count, kept);
+    DS_LAUNCH(vad_tile_scan_kernel, vt.n_utt, VAD_THREADS, (VAD_THREADS + 1) * 8, stream, vt, tile_count, kept);
     const int rc = ds_last_launch_error();
     if (rc) return rc;
-    DS_LAUNCH(vad_scan_kernel, n_dtiles, VAD_THREADS, 2 * VAD_THREADS * 4, stream, mask, vtable, n_utt,
+    DS_LAUNCH(vad_scan_kernel, n_dtiles, VAD_THREADS, 2 * VAD_THREADS * 4, stream, mask, vt,
               (const long long *)tile_count, scan);
     return ds_last_launch_error();
 }
@@ -302,25 +263,16 @@ extern "C" int ds_vad_tile_frames(void) { return VAD_DT; }
 extern "C" int ds_vad_plan(const long long *frame_off, int n_utt, long long *table, long long *counts) {
     DS_REQUIRE(frame_off && counts, DS_ERR_NULL);
     DS_REQUIRE(n_utt > 0, DS_ERR_BAD_SHAPE);
-    long long tiles = 0;
+    ragged_plan<1> plan{table, n_utt};                       // offsets from frame_off[0] on
     for (int u = 0; u < n_utt; ++u) {
         const long long T = frame_off[u + 1] - frame_off[u];
         DS_REQUIRE(T >= 0 && T < (1LL << 31), DS_ERR_BAD_SHAPE);      // the scan inside an utterance is int32
-        const long long nt = (T + VAD_DT - 1) / VAD_DT;
-        if (table) {
-            table[u] = frame_off[u] - frame_off[0];
-            table[n_utt + 1 + u] = tiles;
-            for (long long i = 0; i < nt; ++i) table[2 * (n_utt + 1) + tiles + i] = u;
-        }
-        tiles += nt;
-        DS_REQUIRE(tiles < (1LL << 31), DS_ERR_BAD_SHAPE);
+        plan.add(u, {T}, (T + VAD_DT - 1) / VAD_DT);
+        DS_REQUIRE(plan.tiles < (1LL << 31), DS_ERR_BAD_SHAPE);
     }
-    if (table) {
-        table[n_utt] = frame_off[n_utt] - frame_off[0];
-        table[2 * n_utt + 1] = tiles;
-    }
-    counts[0] = frame_off[n_utt] - frame_off[0];
-    counts[1] = tiles;
+    plan.finish();
+    counts[0] = plan.total[0];
+    counts[1] = plan.tiles;
     counts[2] = VAD_DT;
     return 0;
 }
@@ -345,10 +297,10 @@ extern "C" int ds_vad_log_energy_f32(const void *samples, int in_int16, const lo
     const float log_floor = (float)log((double)floor_v);     // the floor's own log, rounded once: exact at the floor
     if (in_int16)
         DS_LAUNCH_BIG_LDS(vad_energy_kernel<short>, n_tiles, VAD_THREADS, (size_t)lds, stream, (const short *)samples,
-                          table, n_utt, tile_rows, frame_len, frame_step, floor_v, log_floor, out);
+                          ragged_table<2>{table, n_utt}, tile_rows, frame_len, frame_step, floor_v, log_floor, out);
     else
         DS_LAUNCH_BIG_LDS(vad_energy_kernel<float>, n_tiles, VAD_THREADS, (size_t)lds, stream, (const float *)samples,
-                          table, n_utt, tile_rows, frame_len, frame_step, floor_v, log_floor, out);
+                          ragged_table<2>{table, n_utt}, tile_rows, frame_len, frame_step, floor_v, log_floor, out);
     return ds_last_launch_error();
 }
 
@@ -365,15 +317,16 @@ extern "C" int ds_vad_decide(const float *energy, const long long *vtable, int n
     DS_REQUIRE(frames_context <= VAD_MAX_CONTEXT, DS_ERR_UNSUPPORTED);
     double *thr = (double *)workspace;
     long long *tile_count = (long long *)workspace + n_utt;
-    DS_LAUNCH(vad_threshold_kernel, n_utt, VAD_THREADS, VAD_THREADS * 8, stream, energy, vtable, energy_threshold,
-              energy_mean_scale, thr);
+    const ragged_table<1> vt{vtable, n_utt};
+    DS_LAUNCH(vad_threshold_kernel, n_utt, VAD_THREADS, VAD_THREADS * 8, stream, energy, vt,
+              energy_threshold, energy_mean_scale, thr);
     int rc = ds_last_launch_error();
     if (rc) return rc;
     DS_LAUNCH(vad_vote_kernel, n_dtiles, VAD_THREADS, VAD_THREADS * 4 + VAD_DT + 2 * VAD_MAX_CONTEXT, stream, energy,
-              vtable, n_utt, (const double *)thr, frames_context, proportion_threshold, mask, tile_count);
+              vt, (const double *)thr, frames_context, proportion_threshold, mask, tile_count);
     rc = ds_last_launch_error();
     if (rc) return rc;
-    return vad_scan_launch(mask, vtable, n_utt, n_dtiles, tile_count, scan, kept, stream);
+    return vad_scan_launch(mask, vt, n_dtiles, tile_count, scan, kept, stream);
 }
 
 extern "C" int ds_vad_scan(const unsigned char *mask, const long long *vtable, int n_utt, int n_dtiles, int *scan,
@@ -381,10 +334,11 @@ extern "C" int ds_vad_scan(const unsigned char *mask, const long long *vtable, i
     DS_REQUIRE(mask && vtable && scan && kept && workspace, DS_ERR_NULL);
     DS_REQUIRE(n_utt > 0 && n_dtiles > 0, DS_ERR_BAD_SHAPE);
     long long *tile_count = (long long *)workspace + n_utt;
-    DS_LAUNCH(vad_count_kernel, n_dtiles, VAD_THREADS, VAD_THREADS * 4, stream, mask, vtable, n_utt, tile_count);
+    const ragged_table<1> vt{vtable, n_utt};
+    DS_LAUNCH(vad_count_kernel, n_dtiles, VAD_THREADS, VAD_THREADS * 4, stream, mask, vt, tile_count);
     const int rc = ds_last_launch_error();
     if (rc) return rc;
-    return vad_scan_launch(mask, vtable, n_utt, n_dtiles, tile_count, scan, kept, stream);
+    return vad_scan_launch(mask, vt, n_dtiles, tile_count, scan, kept, stream);
 }
 
 extern "C" int ds_vad_select_f32(const float *feat, const unsigned char *mask, const int *scan, const long long *vtable,
@@ -393,7 +347,7 @@ extern "C" int ds_vad_select_f32(const float *feat, const unsigned char *mask, c
     DS_REQUIRE(feat && mask && scan && vtable && ktable && out && workspace, DS_ERR_NULL);
     DS_REQUIRE(n_utt > 0 && n_ktiles > 0 && (tile_rows == 64 || tile_rows == 32), DS_ERR_BAD_SHAPE);
     DS_REQUIRE(nfilt >= 4 && nfilt <= 128 && (nfilt & 3) == 0, DS_ERR_UNSUPPORTED);
-    DS_LAUNCH(vad_select_kernel, n_ktiles, VAD_THREADS, 64 * nfilt + 8 * tile_rows, stream, feat, mask, scan, vtable,
-              ktable, n_utt, nfilt, tile_rows, out, workspace);
+    DS_LAUNCH(vad_select_kernel, n_ktiles, VAD_THREADS, 64 * nfilt + 8 * tile_rows, stream, feat, mask, scan,
+              ragged_table<1>{vtable, n_utt}, ragged_table<2>{ktable, n_utt}, nfilt, tile_rows, out, workspace);
     return ds_last_launch_error();
 }

@@ -155,6 +155,47 @@ def _upload(table: np.ndarray, dev: torch.device) -> torch.Tensor:
     return table_t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else table_t
 
 
+def _ragged_table(sizes: Sequence[np.ndarray], tiles: np.ndarray) -> np.ndarray:
+    """The int64 tile table of csrc/ragged_tiles.h from per-utterance sizes: one column of n_utt + 1 offsets per kind of
+    item, the tiles' offsets, then every tile's utterance."""
+    offs = [np.concatenate([[0], np.cumsum(v)]) for v in (*sizes, tiles)]
+    return np.concatenate(offs + [np.repeat(np.arange(len(tiles)), tiles)]).astype(np.int64)
+
+
+def _ragged_col(table: np.ndarray, c: int, n_utt: int) -> np.ndarray:
+    return table[c * (n_utt + 1):(c + 1) * (n_utt + 1)]
+
+
+def _plan(eng, dev: torch.device, entry: str, host, n_utt: int, args: tuple, n_cols: int, n_counts: int = 3, tails=()):
+    """A `ds_*_plan` entry's two passes over the `host` lengths or offsets, and the upload: the first pass (no table)
+    gives the counts, counts[1] the tiles and with them the length of the table of `n_cols` columns; the second fills
+    it.  `tails`: further int64 host tables (or None) for the same upload, every part padded to an even number of
+    entries (16-byte aligned).  Returns the host table, the counts, the table on `dev` and the tails' views of it."""
+    counts = np.zeros(n_counts, np.int64)
+    host = np.ascontiguousarray(host, np.int64)
+    call = lambda table: eng.lib.call(entry, host.ctypes.data, n_utt, *args, None if table is None else table.ctypes.data,
+                                      counts.ctypes.data)
+    call(None)
+    even = lambda n: (n + 1) & ~1
+    ends = np.cumsum([even((n_cols + 1) * (n_utt + 1) + int(counts[1]))] + [0 if t is None else even(t.size) for t in tails])
+    table = np.zeros(ends[-1], np.int64)
+    call(table)
+    for t, at in zip(tails, ends):
+        if t is not None:
+            table[at:at + t.size] = t.reshape(-1)
+    table_dev = _upload(table, dev)
+    return table, counts, table_dev, [None if t is None else table_dev[at:] for t, at in zip(tails, ends)]
+
+
+def _is_int16(packed: torch.Tensor) -> int:
+    return 1 if packed.dtype == torch.int16 else 0
+
+
+def _workspace(eng, entry: str, *args, dtype=torch.float64, device=None) -> torch.Tensor:
+    """The workspace of 8-byte entries that a `ds_*_workspace_bytes` entry asks for."""
+    return torch.empty(int(eng.lib.raw(entry)(*args)) // 8, dtype=dtype, device=device)
+
+
 MAX_CHANNELS = 8
 
 
@@ -221,20 +262,13 @@ def resample(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], orig_rate: 
     half = zeros * max(L, M)
 
     # output lengths, offsets and the tile table on the host (the lengths are host data)
-    counts = np.zeros(3, np.int64)
-    lens_c = np.ascontiguousarray(lens)
-    plan = lambda table: eng.lib.call("ds_resample_plan", lens_c.ctypes.data, n_utt, L, M, half,
-                                      None if table is None else table.ctypes.data, counts.ctypes.data)
-    plan(None)
+    table, counts, table_dev, _ = _plan(eng, dev, "ds_resample_plan", lens, n_utt, (L, M, half), 2)
     n_out, n_tiles = int(counts[0]), int(counts[1])
-    table = np.zeros(3 * (n_utt + 1) + n_tiles, np.int64)
-    plan(table)
-    out_lens = np.diff(table[n_utt + 1:2 * (n_utt + 1)])
-    table_dev = _upload(table, dev)
+    out_lens = np.diff(_ragged_col(table, 1, n_utt))
 
     taps = _device_taps(L, M, zeros, beta, dev)
     out = torch.empty(n_out, dtype=torch.float32, device=dev)
-    eng.lib.call("ds_resample_poly_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, channels,
+    eng.lib.call("ds_resample_poly_f32", eng._p(packed), _is_int16(packed), channels,
                  eng._p(table_dev), n_utt, n_tiles, eng._p(taps), L, M, half, eng._p(out), eng._stream(out))
     return out, out_lens
 
@@ -414,29 +448,15 @@ def augment(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], plan: Augmen
     n_utt = len(lens)
     rir_tab, max_taps, noise_tab = _augment_tables(plan, n_utt, dev)
 
-    counts = np.zeros(4, np.int64)
-    lens_c = np.ascontiguousarray(lens)
-    tiling = lambda table: eng.lib.call("ds_augment_plan", lens_c.ctypes.data, n_utt,
-                                        None if table is None else table.ctypes.data, counts.ctypes.data)
-    tiling(None)
+    # one upload: the tile table, then the plan's tables
+    _, counts, table_dev, (rir_dev, noise_dev) = _plan(eng, dev, "ds_augment_plan", lens, n_utt, (), 1, n_counts=4,
+                                                       tails=(rir_tab, noise_tab))
     n_total, n_tiles = int(counts[0]), int(counts[1])
-    # one upload: the tile table, then the plan's tables (each at an even entry: 16-byte aligned)
-    n_plan = (2 * (n_utt + 1) + n_tiles + 1) & ~1
-    n_rir = 0 if rir_tab is None else (rir_tab.size + 1) & ~1
-    table = np.zeros(n_plan + n_rir + (0 if noise_tab is None else noise_tab.size), np.int64)
-    tiling(table)
-    if rir_tab is not None:
-        table[n_plan:n_plan + rir_tab.size] = rir_tab.reshape(-1)
-    if noise_tab is not None:
-        table[n_plan + n_rir:] = noise_tab.reshape(-1)
-    table_dev = _upload(table, dev)
-    rir_dev = None if rir_tab is None else table_dev[n_plan:]
-    noise_dev = None if noise_tab is None else table_dev[n_plan + n_rir:]
 
     out = torch.empty(n_total, dtype=torch.float32, device=dev)
-    ws = torch.empty(int(eng.lib.raw("ds_augment_workspace_bytes")(n_tiles)) // 8, dtype=torch.float64, device=dev)
+    ws = _workspace(eng, "ds_augment_workspace_bytes", n_tiles, device=dev)
     stream = eng._stream(out)
-    eng.lib.call("ds_augment_reverb_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, eng._p(table_dev), n_utt,
+    eng.lib.call("ds_augment_reverb_f32", eng._p(packed), _is_int16(packed), eng._p(table_dev), n_utt,
                  n_tiles, None if rir_tab is None else eng._p(plan.rir_bank.samples), eng._p(rir_dev), max_taps,
                  eng._p(out), eng._p(ws), stream)
     if noise_tab is not None:
@@ -455,17 +475,10 @@ def _fbank_plan(eng, lens: np.ndarray, config: FbankConfig, dev: torch.device):
     """Framing on the host (the lengths are host data): (table on the device, frame offsets, frames, tiles, rows per
     tile) of ds_fbank_plan."""
     n_utt = len(lens)
-    counts = np.zeros(3, np.int64)
-    lens_c = np.ascontiguousarray(lens)
-    plan = lambda table: eng.lib.call("ds_fbank_plan", lens_c.ctypes.data, n_utt, config.frame_len, config.frame_step,
-                                      config.nfft, config.nfilt, None if table is None else table.ctypes.data,
-                                      counts.ctypes.data)
-    plan(None)
+    table, counts, table_dev, _ = _plan(eng, dev, "ds_fbank_plan", lens, n_utt,
+                                        (config.frame_len, config.frame_step, config.nfft, config.nfilt), 2)
     n_frames, n_tiles, tile_rows = (int(v) for v in counts)
-    table = np.zeros(3 * (n_utt + 1) + n_tiles, np.int64)
-    plan(table)
-    offsets = table[n_utt + 1:2 * (n_utt + 1)].copy()
-    return _upload(table, dev), offsets, n_frames, n_tiles, tile_rows
+    return table_dev, _ragged_col(table, 1, n_utt).copy(), n_frames, n_tiles, tile_rows
 
 
 @dataclass(frozen=True)
@@ -500,7 +513,7 @@ SELECT_TILE_ROWS = 64                            # rows per workgroup of the sel
 
 def _log_energy(eng, packed, table_dev, n_utt, n_frames, n_tiles, tile_rows, config: FbankConfig, floor: float):
     out = torch.empty(n_frames, dtype=torch.float32, device=packed.device)
-    eng.lib.call("ds_vad_log_energy_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, eng._p(table_dev), n_utt,
+    eng.lib.call("ds_vad_log_energy_f32", eng._p(packed), _is_int16(packed), eng._p(table_dev), n_utt,
                  n_tiles, tile_rows, config.frame_len, config.frame_step, float(floor), eng._p(out), eng._stream(out))
     return out
 
@@ -508,21 +521,14 @@ def _log_energy(eng, packed, table_dev, n_utt, n_frames, n_tiles, tile_rows, con
 def _vad_plan(eng, offsets: np.ndarray, dev: torch.device):
     """(decision table on the device, decision tiles) of ds_vad_plan over the host frame offsets."""
     n_utt = len(offsets) - 1
-    counts = np.zeros(3, np.int64)
-    off_c = np.ascontiguousarray(offsets, np.int64)
-    plan = lambda table: eng.lib.call("ds_vad_plan", off_c.ctypes.data, n_utt, None if table is None else table.ctypes.data,
-                                      counts.ctypes.data)
-    plan(None)
-    n_dtiles = int(counts[1])
-    table = np.zeros(2 * (n_utt + 1) + n_dtiles, np.int64)
-    plan(table)
-    return _upload(table, dev), n_dtiles
+    _, counts, table_dev, _ = _plan(eng, dev, "ds_vad_plan", offsets, n_utt, (), 1)
+    return table_dev, int(counts[1])
 
 
 def _vad_buffers(eng, n_utt, n_frames, n_dtiles, dev):
     scan = torch.empty(n_frames, dtype=torch.int32, device=dev)
     kept = torch.empty(n_utt, dtype=torch.int64, device=dev)
-    ws = torch.empty(int(eng.lib.raw("ds_vad_workspace_bytes")(n_utt, n_dtiles)) // 8, dtype=torch.int64, device=dev)
+    ws = _workspace(eng, "ds_vad_workspace_bytes", n_utt, n_dtiles, dtype=torch.int64, device=dev)
     return scan, kept, ws
 
 
@@ -554,11 +560,9 @@ def _select(eng, feats, mask, scan, kept, vtable_dev):
     out = torch.empty((int(new_off[-1]), nfilt), dtype=torch.float32, device=dev)
     if n_ktiles == 0:
         return out, new_off, None, 0, None
-    ktable = np.concatenate([np.zeros(n_utt + 1, np.int64), new_off, [0], np.cumsum(tiles),
-                             np.repeat(np.arange(n_utt, dtype=np.int64), tiles)]).astype(np.int64)
-    ktable_dev = _upload(ktable, dev)
-    ws = torch.empty(int(eng.lib.raw("ds_fbank_workspace_bytes")(n_utt, n_ktiles, nfilt)) // 8, dtype=torch.float64,
-                     device=dev)
+    # ds_fbank_plan's two columns, because ds_fbank_normalize_f32 reads this table too: no samples, the kept frames
+    ktable_dev = _upload(_ragged_table([np.zeros(n_utt, np.int64), counts], tiles), dev)
+    ws = _workspace(eng, "ds_fbank_workspace_bytes", n_utt, n_ktiles, nfilt, device=dev)
     eng.lib.call("ds_vad_select_f32", eng._p(feats), eng._p(mask), eng._p(scan), eng._p(vtable_dev), eng._p(ktable_dev),
                  n_utt, n_ktiles, nfilt, SELECT_TILE_ROWS, eng._p(out), eng._p(ws), eng._stream(out))
     return out, new_off, ktable_dev, n_ktiles, ws
@@ -662,10 +666,9 @@ def log_mel_fbank(waveforms: Union[Sequence[torch.Tensor], torch.Tensor], config
 
     basis, band, weights, wstride = _device_tables(config, dev)
     out = torch.empty((n_frames, nfilt), dtype=torch.float32, device=dev)
-    ws_bytes = int(eng.lib.raw("ds_fbank_workspace_bytes")(n_utt, n_tiles, nfilt))
-    workspace = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    workspace = _workspace(eng, "ds_fbank_workspace_bytes", n_utt, n_tiles, nfilt, device=dev)
     stream = eng._stream(out)
-    eng.lib.call("ds_fbank_logmel_f32", eng._p(packed), 1 if packed.dtype == torch.int16 else 0, eng._p(table_dev),
+    eng.lib.call("ds_fbank_logmel_f32", eng._p(packed), _is_int16(packed), eng._p(table_dev),
                  n_utt, n_tiles, eng._p(basis), eng._p(band), eng._p(weights), wstride, fl, fs, nfft, nfilt,
                  1 if config.use_logscale else 0, eng._p(out), eng._p(workspace), stream)
     if vad is not None:

@@ -256,6 +256,16 @@ def abi_errors(ctx):
     for rate in (8000, 11025, 16000, 22050, 32000, 44100, 48000, 96000):     # the limit admits every common rate
         L, M = R.ratio(rate, NEW_RATE)
         assert plan(one, L, M, 10 * max(L, M)) == 0, rate
+    # the table entry by entry: utterances of exactly one tile of outputs, one output more, and one output
+    tile = tile_size(lib, 1, 3)
+    lens = np.array([3 * tile, 3 * tile + 1, 1], np.int64)
+    assert plan(lens, 1, 3, 30) == 0 and counts.tolist() == [2 * tile + 2, 4, tile]
+    table = np.full(3 * 4 + 4, -7, np.int64)
+    counts[:] = 0
+    assert lib.raw("ds_resample_plan")(lens.ctypes.data, 3, 1, 3, 30, table.ctypes.data, counts.ctypes.data) == 0
+    assert counts.tolist() == [2 * tile + 2, 4, tile]
+    assert table.tolist() == [0, 3 * tile, 6 * tile + 1, 6 * tile + 2,  0, tile, 2 * tile + 1, 2 * tile + 2,
+                              0, 1, 3, 4,  0, 1, 1, 2]
     # the launch entry validates before it touches anything: placeholders stand for the buffers
     launch = lib.raw("ds_resample_poly_f32")
     p = np.zeros(4, np.int64).ctypes.data

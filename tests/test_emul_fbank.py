@@ -95,6 +95,24 @@ def test_abi_errors():
                                           None) == -3
 
 
+def test_plan_table():
+    """ds_fbank_plan's table entry by entry: utterances of exactly one tile of frames, one frame more, and one frame."""
+    lib = emul_lib()
+    fl, fs = 400, 160
+    counts = np.zeros(3, np.int64)
+    plan = lambda lens, table: lib.raw("ds_fbank_plan")(lens.ctypes.data, len(lens), fl, fs, 512, 64,
+                                                        None if table is None else table.ctypes.data, counts.ctypes.data)
+    assert plan(np.array([1], np.int64), None) == 0
+    tm = int(counts[2])
+    a, b = fl + (tm - 1) * fs, fl + tm * fs                       # tm and tm + 1 frames (framesig)
+    lens = np.array([a, b, 1], np.int64)
+    assert plan(lens, None) == 0 and counts.tolist() == [2 * tm + 2, 4, tm]
+    table = np.full(3 * 4 + 4, -7, np.int64)
+    counts[:] = 0
+    assert plan(lens, table) == 0 and counts.tolist() == [2 * tm + 2, 4, tm]
+    assert table.tolist() == [0, a, a + b, a + b + 1,  0, tm, 2 * tm + 1, 2 * tm + 2,  0, 1, 3, 4,  0, 1, 1, 2]
+
+
 def test_python_errors(features):
     with pytest.raises(DeepSpeakerHipError, match="bad shape"):
         features.log_mel_fbank([torch.zeros(400), torch.zeros(0)])

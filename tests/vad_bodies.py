@@ -350,6 +350,15 @@ def abi_errors(ctx):
     assert plan(np.array([0, 5, 4], np.int64).ctypes.data, 2, None, counts.ctypes.data) == -1         # falling offsets
     tile = tile_frames(lib)
     assert plan(off.ctypes.data, 3, None, counts.ctypes.data) == 0 and counts.tolist() == [2000, 1 + -(-1995 // tile), tile]
+    # the table entry by entry: utterances of exactly one tile of frames, none, one frame more, and one frame; the
+    # offsets need not start at 0
+    off = np.array([5, 5 + tile, 5 + tile, 5 + 2 * tile + 1, 5 + 2 * tile + 2], np.int64)
+    assert plan(off.ctypes.data, 4, None, counts.ctypes.data) == 0 and counts.tolist() == [2 * tile + 2, 4, tile]
+    table = np.full(2 * 5 + 4, -7, np.int64)
+    counts[:] = 0
+    assert plan(off.ctypes.data, 4, table.ctypes.data, counts.ctypes.data) == 0
+    assert counts.tolist() == [2 * tile + 2, 4, tile]
+    assert table.tolist() == [0, tile, tile, 2 * tile + 1, 2 * tile + 2,  0, 1, 1, 3, 4,  0, 2, 2, 3]
     assert lib.raw("ds_vad_workspace_bytes")(0, 1) == -1 and lib.raw("ds_vad_workspace_bytes")(3, 4) == 56
     energy = lib.raw("ds_vad_log_energy_f32")
     assert energy(None, 0, p, 1, 1, 64, 400, 160, 1e-7, p, None) == -3

@@ -134,12 +134,9 @@ def main():
 
         # the reverberation kernel alone, on tables already on the device
         rir_tab, max_taps, _ = F._augment_tables(plan, args.utts, x.device)
-        counts = np.zeros(4, np.int64)
-        eng.lib.call("ds_augment_plan", lens.ctypes.data, args.utts, None, counts.ctypes.data)
+        _, counts, table_dev, (rir_dev,) = F._plan(eng, x.device, "ds_augment_plan", lens, args.utts, (), 1, n_counts=4,
+                                                   tails=(rir_tab,))
         n_tiles = int(counts[1])
-        table = np.zeros(2 * (args.utts + 1) + n_tiles, np.int64)
-        eng.lib.call("ds_augment_plan", lens.ctypes.data, args.utts, table.ctypes.data, counts.ctypes.data)
-        table_dev, rir_dev = torch.from_numpy(table).cuda(), torch.from_numpy(rir_tab.reshape(-1)).cuda()
         out = torch.empty(n_in, dtype=torch.float32, device="cuda")
         ws = torch.empty(3 * n_tiles, dtype=torch.float64, device="cuda")
         kernel = lambda: eng.lib.call("ds_augment_reverb_f32", eng._p(x), 0, eng._p(table_dev), args.utts, n_tiles,
