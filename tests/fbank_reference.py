@@ -53,14 +53,15 @@ def filterbank(nfilt=64, nfft=512, sample_rate=16000):
     return w
 
 
-def frames(x, sample_rate=16000):
-    """[n_frames, frame_len] float64 frames of the pre-emphasised, zero-padded signal (rectangular window)."""
-    fl, fs = frame_params(sample_rate)
+def frames(x, sample_rate=16000, winlen=0.025, winstep=0.01, dtype=np.float64):
+    """[n_frames, frame_len] frames (float64 unless `dtype` says otherwise) of the pre-emphasised, zero-padded signal
+    (rectangular window)."""
+    fl, fs = frame_params(sample_rate, winlen, winstep)
     if len(x) == 0:
         raise ValueError("empty signal")
-    y = preemphasis(x).astype(np.float64)
+    y = preemphasis(x).astype(dtype)
     nf = n_frames(len(y), fl, fs)
-    pad = np.concatenate([y, np.zeros((nf - 1) * fs + fl - len(y))])
+    pad = np.concatenate([y, np.zeros(max(0, (nf - 1) * fs + fl - len(y)), dtype)])
     idx = np.arange(fl)[None, :] + fs * np.arange(nf)[:, None]
     return pad[idx]
 
@@ -69,8 +70,8 @@ def power_spectrum(fr, nfft=512):
     return np.abs(np.fft.rfft(fr, nfft)) ** 2 / nfft
 
 
-def fbank(x, sample_rate=16000, nfilt=64, nfft=512, use_logscale=True):
-    fb = power_spectrum(frames(x, sample_rate), nfft) @ filterbank(nfilt, nfft, sample_rate).T
+def fbank(x, sample_rate=16000, nfilt=64, nfft=512, use_logscale=True, winlen=0.025, winstep=0.01):
+    fb = power_spectrum(frames(x, sample_rate, winlen, winstep), nfft) @ filterbank(nfilt, nfft, sample_rate).T
     fb = np.where(fb == 0, np.finfo(float).eps, fb)
     if use_logscale:
         fb = 20 * np.log10(np.maximum(fb, 1e-5))
@@ -83,12 +84,63 @@ def normalize_frames(m, scale=False):
     return m - np.mean(m, axis=0)
 
 
-def mk_mfb(x, sample_rate=16000, nfilt=64, nfft=512, normalize="mean", use_logscale=True):
+def mk_mfb(x, sample_rate=16000, nfilt=64, nfft=512, normalize="mean", use_logscale=True, winlen=0.025, winstep=0.01):
     """float64 [T, nfilt]; normalize in {"mean", "mean_std", None}"""
-    fb = fbank(x, sample_rate, nfilt, nfft, use_logscale)
+    fb = fbank(x, sample_rate, nfilt, nfft, use_logscale, winlen, winstep)
     if normalize is None:
         return fb
     return normalize_frames(fb, scale=normalize == "mean_std")
+
+
+def dft_table_f32(frame_len, nfft):
+    """float32 (cos, sin) tables [frame_len, nfft/2+1] of the DFT, from its definition X_k = sum_n x_n exp(-2 pi i n k /
+    nfft): the angle reduced exactly in integers, evaluated in float64 and rounded once."""
+    n = np.arange(frame_len, dtype=np.int64)[:, None]
+    k = np.arange(nfft // 2 + 1, dtype=np.int64)[None, :]
+    ang = 2.0 * np.pi * ((n * k) % nfft) / nfft
+    return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
+
+
+def mk_mfb_f32(x, sample_rate=16000, nfilt=64, nfft=512, normalize="mean", use_logscale=True, winlen=0.025, winstep=0.01):
+    """The same pipeline with the spectrum in float32, as a kernel that does the DFT as a float32 matrix product has it:
+    float32 pre-emphasised frames times float32 cos / sin tables, the power formed from those float32 sums and stored in
+    float32; then float32-rounded mel weights, floor and log in float64, the float32 store, and the normalisation in
+    float64 over the stored values, stored in float32 again.  Its distance from `mk_mfb` is what float32 arithmetic costs
+    this operation: it sizes the tests' bars.  Returns float32 [T, nfilt].
+
+    The product is summed over the frame's samples in their order, every product and every sum rounded to float32: the
+    plain order, and the same on every host (`fr @ cos` would sum in whatever blocks the host's BLAS build chooses for
+    its processor, so the bar would depend on the machine that runs the test)."""
+    fl, _ = frame_params(sample_rate, winlen, winstep)
+    fr = frames(x, sample_rate, winlen, winstep, dtype=np.float32)
+    assert fr.dtype == np.float32
+    cos, sin = dft_table_f32(fl, nfft)
+    re, im = np.zeros((len(fr), nfft // 2 + 1), np.float32), np.zeros((len(fr), nfft // 2 + 1), np.float32)
+    for n in range(fl):
+        col = fr[:, n, None]
+        re += col * cos[n]
+        im += col * sin[n]
+    assert re.dtype == np.float32
+    re, im = re.astype(np.float64), im.astype(np.float64)
+    pw = ((re * re + im * im) / nfft).astype(np.float32)
+    w = filterbank(nfilt, nfft, sample_rate).astype(np.float32)
+    fb = pw.astype(np.float64) @ w.astype(np.float64).T
+    fb = np.where(fb == 0, np.finfo(float).eps, fb)
+    if use_logscale:
+        fb = 20 * np.log10(np.maximum(fb, 1e-5))
+    fb = fb.astype(np.float32)
+    if normalize is None:
+        return fb
+    return normalize_frames(fb.astype(np.float64), scale=normalize == "mean_std").astype(np.float32)
+
+
+def level_steps(seed, n, frame_step, decades=6):
+    """Seeded float32 noise whose level falls by a factor of 10 every `frame_step` samples, cycling over `decades`
+    decades: neighbouring frames differ by orders of magnitude, so a frame in the wrong row cannot pass for its
+    neighbour."""
+    rs = np.random.RandomState(seed)
+    level = 10.0 ** -((np.arange(n) // frame_step) % decades)
+    return (0.5 * np.clip(rs.randn(n) / 3.0, -1.0, 1.0) * level).astype(np.float32)
 
 
 def synthetic_audio(seed, n, sample_rate=16000, kind="noise"):

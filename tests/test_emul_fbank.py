@@ -1,156 +1,142 @@
 """CPU: the filterbank front end (csrc/fbank.hip, features.py) through the host emulator of the kernels, against the
-float64 restatement of mk_MFB (tests/fbank_reference.py)."""
+float64 restatement of mk_MFB (tests/fbank_reference.py).  The cases are tests/fbank_bodies.py, shared with
+tests/test_gpu_fbank.py; the restatements themselves are checked here."""
 import numpy as np
 import pytest
-import torch
 
+import fbank_bodies as B
 import fbank_reference as R
 from emul_util import emul_lib
 
-from deepspeaker_pytorch_amd._native import DeepSpeakerHipError
 from deepspeaker_pytorch_amd.engine import Engine
 
-TOL_DB = 5e-4
+TOL_DB = B.TOL_DB
 
 
 @pytest.fixture
-def features():
+def ctx():
     from deepspeaker_pytorch_amd import data, features
     eng = Engine(emul_lib())
     features._engine_override = eng
     data._engine_override = eng
     try:
-        yield features
+        yield B.Ctx(features, "cpu", emul_lib())
     finally:
         features._engine_override = None
         data._engine_override = None
 
 
+# ---- the restatements alone ----
+def test_window_keywords_default_to_the_reference():
+    """winlen / winstep default to the reference's 0.025 / 0.01; other values reach the framing"""
+    x = R.synthetic_audio(1, 3000, kind="ar")
+    np.testing.assert_array_equal(R.mk_mfb(x), R.mk_mfb(x, winlen=0.025, winstep=0.01))
+    np.testing.assert_array_equal(R.frames(x), R.frames(x, 16000, 0.025, 0.01))
+    assert R.frames(x).shape == (R.n_frames(3000, 400, 160), 400)
+    fr = R.frames(x, 16000, 401 / 16000, 0.03)
+    assert fr.shape == (R.n_frames(3000, 401, 480), 401) == (7, 401)
+    y = R.preemphasis(x).astype(np.float64)
+    np.testing.assert_array_equal(fr[2], y[960:1361])
+    np.testing.assert_array_equal(fr[6], np.concatenate([y[2880:], np.zeros(401 - 120)]))
+    assert R.fbank(x, winlen=401 / 16000, winstep=0.03).shape == (7, 64)
+    assert R.frame_params(22050) == (551, 221)
+
+
+def test_float32_restatement_is_the_same_operation():
+    """mk_mfb_f32 differs from mk_mfb by float32 rounding and nothing else; a one-sample frame has a flat spectrum"""
+    for kw in (dict(), dict(sample_rate=22050, nfft=1024), dict(sample_rate=2000, nfft=64, nfilt=12),
+               dict(winlen=401 / 16000, winstep=0.03)):
+        x = R.synthetic_audio(2, 5000, kw.get("sample_rate", 16000), "ar")
+        for normalize in (None, "mean", "mean_std"):
+            a, b = R.mk_mfb_f32(x, normalize=normalize, **kw), R.mk_mfb(x, normalize=normalize, **kw)
+            assert a.dtype == np.float32 and a.shape == b.shape
+            assert np.abs(a - b).max() <= 1e-4, (kw, normalize)
+        a, b = (f(x, normalize=None, use_logscale=False, **kw) for f in (R.mk_mfb_f32, R.mk_mfb))
+        assert B.frame_rel(a, b) <= 1e-5, kw
+    one = R.mk_mfb_f32(np.array([0.5], np.float32), normalize=None, use_logscale=False)
+    want = (0.25 / 512) * R.filterbank().sum(1)
+    np.testing.assert_allclose(one[0], np.where(want == 0, np.finfo(float).eps, want), rtol=1e-6)
+
+
+def test_level_steps_tell_frames_apart():
+    """a frame of the stepped signal stored one row off is wrong by orders of magnitude under the per-frame metric"""
+    x = R.level_steps(3, 400 + 30 * 160, 160)
+    ref = R.mk_mfb(x, normalize=None, use_logscale=False)
+    for shift in (1, -1):
+        moved = np.roll(ref, shift, axis=0)
+        assert B.frame_rel(moved, ref) > 10.0
+        per_frame = np.abs(moved - ref).max(1) / np.abs(ref).max(1)
+        # most frames are wrong by their own size or more; the two of every six that hold the same loud step whole
+        # have nearly the same power spectrum, and even they are a hundred times over bars near 1e-6
+        assert (per_frame > 0.5).mean() >= 0.75 and per_frame.min() > 1e-4
+
+
+# ---- the kernels through the emulator ----
 LENGTHS = (1, 399, 400, 401, 2000)
 
 
 @pytest.mark.parametrize("sr", [16000, 8000])
 @pytest.mark.parametrize("normalize", ["mean", "mean_std", None])
-def test_log_mel_fbank_matches_restatement(features, sr, normalize):
+def test_log_mel_fbank_matches_restatement(ctx, sr, normalize):
     kinds = ("noise", "tone", "ar", "chirp", "quiet_noise")
-    xs = [R.synthetic_audio(10 + i, n, sr, kinds[i]) for i, n in enumerate(LENGTHS)]
-    cfg = features.FbankConfig(sample_rate=sr)
-    out, off = features.log_mel_fbank([torch.from_numpy(x) for x in xs], cfg, normalize=normalize)
-    out = out.numpy()
-    assert out.dtype == np.float32 and out.shape[1] == 64
-    fl, fs = R.frame_params(sr)
-    assert off.tolist() == np.concatenate([[0], np.cumsum([R.n_frames(n, fl, fs) for n in LENGTHS])]).tolist()
-    for u, x in enumerate(xs):
-        ref = R.mk_mfb(x, sample_rate=sr, normalize=normalize)
-        err = np.abs(out[off[u]:off[u + 1]] - ref).max()
-        assert err <= TOL_DB, (u, err)
+    B.restatement(ctx, [R.synthetic_audio(10 + i, n, sr, kinds[i]) for i, n in enumerate(LENGTHS)], sr, normalize)
 
 
-def test_int16_input_is_the_scaled_float_input(features):
-    xs = [R.int16_quantised(R.synthetic_audio(20 + i, n, kind="ar")) for i, n in enumerate((401, 2000))]
-    a, off = features.log_mel_fbank([torch.from_numpy(x) for x in xs])
-    b, _ = features.log_mel_fbank([torch.from_numpy(x.astype(np.float32) / 32768.0) for x in xs])
-    np.testing.assert_array_equal(a.numpy().view(np.int32), b.numpy().view(np.int32))
-    for u, x in enumerate(xs):
-        ref = R.mk_mfb(x.astype(np.float32) / np.float32(32768.0))
-        assert np.abs(a.numpy()[off[u]:off[u + 1]] - ref).max() <= TOL_DB
+def test_int16_input_is_the_scaled_float_input(ctx):
+    B.int16_is_scaled_float(ctx, [R.int16_quantised(R.synthetic_audio(20 + i, n, kind="ar"))
+                                  for i, n in enumerate((401, 2000))], "mean", values=True)
 
 
-def test_packed_input_and_feature_store(features):
-    from deepspeaker_pytorch_amd import data
-    xs = [R.synthetic_audio(30 + i, n, kind="noise") for i, n in enumerate((900, 2000))]
-    packed = torch.from_numpy(np.concatenate(xs))
-    a, off = features.log_mel_fbank(packed, lengths=[900, 2000])
-    b, _ = features.log_mel_fbank([torch.from_numpy(x) for x in xs])
-    assert torch.equal(a, b)
-    fs = data.FeatureStore.from_waveforms([torch.from_numpy(x) for x in xs])
-    assert len(fs) == 2 and fs.n_feat == 64 and fs.offsets.tolist() == off.tolist()
-    assert torch.equal(fs.features, a)
-    crop = fs.crops([1], [3], 8).numpy()
-    np.testing.assert_array_equal(crop[0, 0], a.numpy()[off[1] + 3:off[1] + 11])
+def test_packed_input_and_feature_store(ctx):
+    B.packed_input_and_feature_store(ctx)
 
 
-def test_raw_filterbank(features):
-    x = R.synthetic_audio(41, 300, kind="noise")
-    cfg = features.FbankConfig(use_logscale=False)
-    out, _ = features.log_mel_fbank([torch.from_numpy(x)], cfg, normalize=None)
-    ref = R.mk_mfb(x, normalize=None, use_logscale=False)
-    np.testing.assert_allclose(out.numpy(), ref, rtol=2e-5, atol=1e-9)
+def test_raw_filterbank(ctx):
+    B.raw_filterbank(ctx, 41, 300, "noise", rtol=2e-5, atol=1e-9)
 
 
-def test_abi_errors():
-    lib = emul_lib()
-    counts = np.zeros(3, np.int64)
-    plan = lambda lens, fl, fs, nfft, nfilt: lib.raw("ds_fbank_plan")(lens.ctypes.data, len(lens), fl, fs, nfft, nfilt,
-                                                                       None, counts.ctypes.data)
-    assert plan(np.array([400, 0], np.int64), 400, 160, 512, 64) == -1          # empty signal
-    one = np.array([400], np.int64)
-    assert plan(one, 600, 240, 512, 64) == -4                                     # frame_len > nfft
-    assert plan(one, 400, 160, 512, 62) == -4                                     # nfilt % 4 != 0
-    assert plan(one, 400, 160, 500, 64) == -4                                     # nfft not a power of two
-    assert plan(one, 400, 160, 512, 64) == 0 and counts.tolist() == [1, 1, 64]
-    assert plan(np.array([160 * 48000 + 1], np.int64), 400, 160, 512, 64) == 0
-    assert counts.tolist() == [R.n_frames(160 * 48000 + 1, 400, 160), 750, 64]      # an 8-minute utterance
-    assert lib.raw("ds_fbank_logmel_f32")(None, 0, None, 1, 1, None, None, None, 1, 400, 160, 512, 64, 1, None, None,
-                                          None) == -3
+def test_abi_errors(ctx):
+    B.abi_errors(ctx)
 
 
-def test_plan_table():
-    """ds_fbank_plan's table entry by entry: utterances of exactly one tile of frames, one frame more, and one frame."""
-    lib = emul_lib()
-    fl, fs = 400, 160
-    counts = np.zeros(3, np.int64)
-    plan = lambda lens, table: lib.raw("ds_fbank_plan")(lens.ctypes.data, len(lens), fl, fs, 512, 64,
-                                                        None if table is None else table.ctypes.data, counts.ctypes.data)
-    assert plan(np.array([1], np.int64), None) == 0
-    tm = int(counts[2])
-    a, b = fl + (tm - 1) * fs, fl + tm * fs                       # tm and tm + 1 frames (framesig)
-    lens = np.array([a, b, 1], np.int64)
-    assert plan(lens, None) == 0 and counts.tolist() == [2 * tm + 2, 4, tm]
-    table = np.full(3 * 4 + 4, -7, np.int64)
-    counts[:] = 0
-    assert plan(lens, table) == 0 and counts.tolist() == [2 * tm + 2, 4, tm]
-    assert table.tolist() == [0, a, a + b, a + b + 1,  0, tm, 2 * tm + 1, 2 * tm + 2,  0, 1, 3, 4,  0, 1, 1, 2]
+def test_plan_table(ctx):
+    B.plan_table(ctx)
 
 
-def test_python_errors(features):
-    with pytest.raises(DeepSpeakerHipError, match="bad shape"):
-        features.log_mel_fbank([torch.zeros(400), torch.zeros(0)])
-    with pytest.raises(DeepSpeakerHipError):
-        features.log_mel_fbank([torch.zeros(400)], features.FbankConfig(sample_rate=24000))   # frame_len 600 > nfft 512
-    with pytest.raises(DeepSpeakerHipError):
-        features.log_mel_fbank([torch.zeros(400)], features.FbankConfig(nfilt=30))
-    with pytest.raises(ValueError):
-        features.log_mel_fbank([torch.zeros(400)], normalize="std")
-    with pytest.raises(ValueError):
-        features.log_mel_fbank([torch.zeros(400, dtype=torch.float64)])
+def test_python_errors(ctx):
+    B.python_errors(ctx)
 
 
 @pytest.mark.parametrize("sr,nfft,nfilt", [(40000, 1024, 64), (2000, 64, 16), (16000, 512, 128), (8000, 256, 32)])
-def test_other_configurations(features, sr, nfft, nfilt):
-    """Other sample rates, FFT sizes and filter counts; (40000, 1024) takes 32-frame tiles (the 64-frame tile's samples
-    and power spectrum do not fit the LDS together)."""
-    lib = emul_lib()
-    cfg = features.FbankConfig(sample_rate=sr, nfft=nfft, nfilt=nfilt)
-    n = (70 * cfg.frame_step + cfg.frame_len)                      # more than one tile of either size
-    xs = [R.synthetic_audio(50, n, sr, "ar"), R.synthetic_audio(51, n // 3, sr, "noise")]
-    counts = np.zeros(3, np.int64)
-    lens = np.array([len(x) for x in xs], np.int64)
-    assert lib.raw("ds_fbank_plan")(lens.ctypes.data, 2, cfg.frame_len, cfg.frame_step, nfft, nfilt, None,
-                                    counts.ctypes.data) == 0
-    assert counts[2] == (32 if nfft == 1024 else 64)
-    out, off = features.log_mel_fbank([torch.from_numpy(x) for x in xs], cfg, normalize="mean")
-    for u, x in enumerate(xs):
-        ref = R.mk_mfb(x, sample_rate=sr, nfilt=nfilt, nfft=nfft, normalize="mean")
-        assert np.abs(out.numpy()[off[u]:off[u + 1]] - ref).max() <= TOL_DB
+def test_other_configurations(ctx, sr, nfft, nfilt):
+    B.other_configurations(ctx, sr, nfft, nfilt)
 
 
-def test_preemphasis_bits():
-    lib = emul_lib()
-    x = R.synthetic_audio(60, 5000, kind="ar")
-    y = np.zeros(len(x), np.float32)
-    assert lib.raw("ds_fbank_preemphasis_f32")(x.ctypes.data, 0, len(x), y.ctypes.data, None) == 0
-    np.testing.assert_array_equal(y.view(np.int32), R.preemphasis(x).view(np.int32))
-    q = R.int16_quantised(x)
-    assert lib.raw("ds_fbank_preemphasis_f32")(q.ctypes.data, 1, len(q), y.ctypes.data, None) == 0
-    np.testing.assert_array_equal(y.view(np.int32), R.preemphasis(q.astype(np.float32) / np.float32(32768)).view(np.int32))
+def test_preemphasis_bits(ctx):
+    B.preemphasis_bits(ctx, 60, 5000)
+
+
+def test_deterministic_and_batch_invariant(ctx):
+    B.deterministic(ctx, n_utt=12, n_max=6000, picks=(0, 5, 11))
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("name", list(B.CONFS))
+def test_configuration(ctx, name, dtype):
+    B.configuration(ctx, name, dtype)
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("name", list(B.CONFS))
+def test_loud_successor(ctx, name, dtype):
+    B.loud_successor(ctx, name, dtype)
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("name", [n for n, c in B.CONFS.items() if c.long])
+def test_statistics_alone_and_last_of_five(ctx, name, dtype):
+    B.statistics_alone_and_last_of_five(ctx, name, dtype)
+
+
+def test_every_instantiation_was_launched(ctx):
+    B.coverage(ctx)

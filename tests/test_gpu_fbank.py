@@ -1,23 +1,28 @@
 """MI355X: the log-mel filterbank front end (csrc/fbank.hip, features.py, FeatureStore.from_waveforms) against the
-float64 restatement of the reference's mk_MFB (tests/fbank_reference.py), on seeded synthetic audio."""
+float64 restatement of the reference's mk_MFB (tests/fbank_reference.py), on seeded synthetic audio.  The cases are
+tests/fbank_bodies.py, the same ones tests/test_emul_fbank.py runs through the host emulator; the 8-minute utterance and
+waveforms-to-embeddings are the device's alone."""
 import numpy as np
 import pytest
 import torch
 
+import fbank_bodies as B
 import fbank_reference as R
 
 pytestmark = pytest.mark.gpu
 
 # max |feature - restatement| in dB (in normalised units for "mean_std"): measured on the MI355X at most 2.1e-4 over
 # every signal here, the 8-minute utterance included
-TOL_DB = 5e-4
+TOL_DB = B.TOL_DB
 KINDS = ("noise", "quiet_noise", "tone", "quiet_tone", "chirp", "silence", "dc", "ar")
 LENGTHS = (1, 399, 400, 401, 560, 561, 16000, 48000)
 
 
-def _features():
+@pytest.fixture
+def ctx():
     from deepspeaker_pytorch_amd import features
-    return features
+    from deepspeaker_pytorch_amd.model import get_engine
+    return B.Ctx(features, "cuda", get_engine().lib)
 
 
 def _signals(sr=16000):
@@ -28,30 +33,16 @@ def _signals(sr=16000):
     return out
 
 
-def _max_err(out, off, refs):
-    return max(float(np.abs(out[off[u]:off[u + 1]] - r).max()) for u, r in enumerate(refs))
-
-
 @pytest.mark.parametrize("sr", [16000, 8000])
 @pytest.mark.parametrize("normalize", [None, "mean", "mean_std"])
-def test_features_match_restatement(sr, normalize):
-    F = _features()
+def test_features_match_restatement(ctx, sr, normalize):
     xs = _signals(sr)
-    xs += [R.int16_quantised(x) for x in xs[::5]]
-    refs = [R.mk_mfb(x.astype(np.float32) / np.float32(32768) if x.dtype == np.int16 else x, sample_rate=sr,
-                     normalize=normalize) for x in xs]
-    f32 = [x for x in xs if x.dtype == np.float32]
-    i16 = [x for x in xs if x.dtype == np.int16]
-    out, off = F.log_mel_fbank([torch.from_numpy(x).cuda() for x in f32], F.FbankConfig(sample_rate=sr), normalize)
-    out16, off16 = F.log_mel_fbank([torch.from_numpy(x).cuda() for x in i16], F.FbankConfig(sample_rate=sr), normalize)
-    err = max(_max_err(out.cpu().numpy(), off, refs[:len(f32)]), _max_err(out16.cpu().numpy(), off16, refs[len(f32):]))
-    print(f"fbank sr={sr} normalize={normalize}: max abs error {err:.3e}")
-    assert err <= TOL_DB, err
+    B.restatement(ctx, xs + [R.int16_quantised(x) for x in xs[::5]], sr, normalize)
 
 
-def test_eight_minute_utterance():
+def test_eight_minute_utterance(ctx):
     """48k frames: the per-utterance statistics come from 750 tiles' f64 partials."""
-    F = _features()
+    F = ctx.features
     sr, n = 16000, 16000 * 480
     rs = np.random.RandomState(7)
     t = np.arange(n) / sr
@@ -66,51 +57,28 @@ def test_eight_minute_utterance():
         assert err <= TOL_DB, err
 
 
-def test_preemphasis_bits():
-    from deepspeaker_pytorch_amd.model import get_engine
-    eng = get_engine()
-    x = R.synthetic_audio(3, 100000, kind="ar")
-    for src, ref in ((x, R.preemphasis(x)),
-                     (R.int16_quantised(x), R.preemphasis(R.int16_quantised(x).astype(np.float32) / np.float32(32768)))):
-        d = torch.from_numpy(src).cuda()
-        y = torch.empty(len(src), dtype=torch.float32, device="cuda")
-        eng.lib.call("ds_fbank_preemphasis_f32", eng._p(d), 1 if src.dtype == np.int16 else 0, len(src), eng._p(y),
-                     eng._stream(y))
-        np.testing.assert_array_equal(y.cpu().numpy().view(np.int32), ref.view(np.int32))
+def test_preemphasis_bits(ctx):
+    B.preemphasis_bits(ctx, 3, 100000)
 
 
-def test_raw_single_frame_filterbank():
-    F = _features()
-    x = R.synthetic_audio(5, 400, kind="ar")
-    out, _ = F.log_mel_fbank([torch.from_numpy(x).cuda()], F.FbankConfig(use_logscale=False), normalize=None)
-    ref = R.mk_mfb(x, normalize=None, use_logscale=False)
-    np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=1e-5, atol=1e-12)
+def test_raw_single_frame_filterbank(ctx):
+    B.raw_filterbank(ctx, 5, 400, "ar", rtol=1e-5, atol=1e-12)
 
 
-def test_int16_is_bit_identical_to_scaled_float():
-    F = _features()
-    q = [R.int16_quantised(x) for x in _signals()[::3]]
-    a, _ = F.log_mel_fbank([torch.from_numpy(x).cuda() for x in q], normalize="mean_std")
-    b, _ = F.log_mel_fbank([torch.from_numpy(x.astype(np.float32) / np.float32(32768)).cuda() for x in q],
-                           normalize="mean_std")
-    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+def test_raw_filterbank(ctx):
+    B.raw_filterbank(ctx, 41, 300, "noise", rtol=2e-5, atol=1e-9)
 
 
-def test_deterministic_and_batch_invariant():
-    F = _features()
-    rs = np.random.RandomState(11)
-    kinds = ("noise", "ar", "chirp", "tone")
-    xs = [torch.from_numpy(R.synthetic_audio(1000 + i, int(rs.randint(1, 160000)), kind=kinds[i % 4])).cuda()
-          for i in range(100)]
-    for normalize in ("mean", "mean_std", None):
-        a, off = F.log_mel_fbank(xs, normalize=normalize)
-        b, _ = F.log_mel_fbank(xs, normalize=normalize)
-        assert torch.equal(a, b)
-        for u in (0, 17, 63, 99):
-            alone, _ = F.log_mel_fbank([xs[u]], normalize=normalize)
-            assert torch.equal(alone, a[off[u]:off[u + 1]]), (normalize, u)
-        packed, off2 = F.log_mel_fbank(torch.cat(xs), lengths=[len(x) for x in xs], normalize=normalize)
-        assert torch.equal(packed, a) and off2.tolist() == off.tolist()
+def test_int16_is_bit_identical_to_scaled_float(ctx):
+    B.int16_is_scaled_float(ctx, [R.int16_quantised(x) for x in _signals()[::3]], "mean_std", values=False)
+
+
+def test_deterministic_and_batch_invariant(ctx):
+    B.deterministic(ctx, n_utt=100, n_max=160000, picks=(0, 17, 63, 99))
+
+
+def test_packed_input_and_feature_store(ctx):
+    B.packed_input_and_feature_store(ctx)
 
 
 def test_end_to_end_waveforms_to_embeddings():
@@ -142,13 +110,40 @@ def test_end_to_end_waveforms_to_embeddings():
         assert np.abs(crops[b, 0] - ref).max() <= TOL_DB
 
 
-def test_errors_raise():
-    from deepspeaker_pytorch_amd._native import DeepSpeakerHipError
-    F = _features()
-    x = torch.zeros(1000, device="cuda")
-    with pytest.raises(DeepSpeakerHipError, match="bad shape"):
-        F.log_mel_fbank([x, torch.zeros(0, device="cuda")])
-    with pytest.raises(DeepSpeakerHipError):
-        F.log_mel_fbank([x], F.FbankConfig(sample_rate=24000))            # frame_len 600 > nfft 512
-    with pytest.raises(DeepSpeakerHipError):
-        F.log_mel_fbank([x], F.FbankConfig(nfilt=66))
+def test_errors_raise(ctx):
+    B.python_errors(ctx)
+
+
+def test_abi_errors(ctx):
+    B.abi_errors(ctx)
+
+
+def test_plan_table(ctx):
+    B.plan_table(ctx)
+
+
+@pytest.mark.parametrize("sr,nfft,nfilt", [(40000, 1024, 64), (2000, 64, 16), (16000, 512, 128), (8000, 256, 32)])
+def test_other_configurations(ctx, sr, nfft, nfilt):
+    B.other_configurations(ctx, sr, nfft, nfilt)
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("name", list(B.CONFS))
+def test_configuration(ctx, name, dtype):
+    B.configuration(ctx, name, dtype)
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("name", list(B.CONFS))
+def test_loud_successor(ctx, name, dtype):
+    B.loud_successor(ctx, name, dtype)
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("name", [n for n, c in B.CONFS.items() if c.long])
+def test_statistics_alone_and_last_of_five(ctx, name, dtype):
+    B.statistics_alone_and_last_of_five(ctx, name, dtype)
+
+
+def test_every_instantiation_was_launched(ctx):
+    B.coverage(ctx)
