@@ -225,6 +225,11 @@ _SIGNATURES = {
     "ds_augment_reverb_f32": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
     "ds_augment_mix_f32": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, _P]),
     "ds_augment_level_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "ds_ahc_plan": (c_int, [_P, c_int, c_int, _P, _P]),
+    "ds_ahc_workspace_bytes": (c_longlong, [_P, c_int]),
+    "ds_ahc_distances_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "ds_ahc_linkage_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "ds_ahc_cut": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_float, c_int, _P, c_int, c_int, _P, _P, _P]),
 }
 
 

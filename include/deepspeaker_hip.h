@@ -903,6 +903,51 @@ int ds_augment_mix_f32(float *data, const long long *table, int n_utt, int n_til
 int ds_augment_level_f32(float *data, const long long *table, int n_utt, int n_tiles, int mixed, const double *workspace,
                          void *stream);
 
+/* ---- speaker diarisation (csrc/ahc.hip): within-recording distance matrices of a packed batch of recordings and their
+ * agglomerative hierarchical clustering, one recording per workgroup.  Recording r owns rows row_off[r] .. row_off[r+1]
+ * of emb[N,D] (n_r of them, 0 <= n_r <= DS_AHC_MAX_N); its n_r x n_r f32 matrix lies at entry sum_{q<r} n_q^2 of the
+ * packed matrices, its n_r - 1 merge steps at sum_{q<r} max(n_q - 1, 0) of the step arrays, its leaves at row_off[r].
+ * Every buffer is the caller's; nothing is allocated, read back or synchronised, and no kernel uses an atomic or waits
+ * for another workgroup.  A recording's results are bit-identical whatever else is in the batch.
+ * ds_ahc_plan (HOST): from the host offsets row_off[n_rec + 1] (row_off[0] == 0).  With table == NULL only counts[6] =
+ *   {total rows, distance tiles, rows per tile, matrix entries, merge steps, largest n_r} is written; otherwise also
+ *   the int64 table row_off | mat_off | step_off | tile_off (n_rec + 1 entries each) | tile_rec[tiles], which the caller
+ *   copies to the device.  A tile is a (rows per tile)^2 block of one recording's upper triangle.  Offsets that
+ *   decrease, n_r above DS_AHC_MAX_N, D < 1 or D > DS_NEAREST_MAX_D: DS_ERR_BAD_SHAPE.
+ * ds_ahc_workspace_bytes (HOST): the bytes of the packed matrices, the work area that the linkage consumes; -1 for
+ *   offsets that ds_ahc_plan refuses.
+ * ds_ahc_distances_f32: entry (i, j), i != j, is ds_pairwise_distance_f32 of rows i and j bit for bit (direct
+ *   differences, eps = 1e-4 / D inside the root); computed once for i < j and stored on both sides; +inf on the
+ *   diagonal.  n_tiles, tile_rows: counts[1], counts[2] of the plan for the same D.
+ * ds_ahc_linkage_f32: the n_r - 1 merges of every recording, IN PLACE over its matrix (symmetric, NaN-free; consumed).
+ *   Step s merges the active pair (a, b), a < b, with the smallest current distance, ties to the smallest a, then the
+ *   smallest b.  The cluster lives on in slot a (a cluster's slot is its lowest member).  For every other active k:
+ *     DS_AHC_SINGLE min(d_ak, d_bk); DS_AHC_COMPLETE max(d_ak, d_bk);
+ *     DS_AHC_AVERAGE ((float)n_a * d_ak + (float)n_b * d_bk) / (float)(n_a + n_b): both products, the sum and the
+ *     division each rounded to f32 (no fused multiply-add),
+ *   written to row and column a.  pair [steps][2] int32 = (a, b); height [steps] f32 = the merged distance; size
+ *   [steps] int32 = n_a + n_b; into / step [rows] int32 = the slot that absorbed slot i and at which step (-1, -1 for
+ *   the survivor).  n_max: the largest n_r (counts[5]); above DS_AHC_MAX_N: DS_ERR_BAD_SHAPE; another method:
+ *   DS_ERR_UNSUPPORTED.
+ * ds_ahc_cut: labels [rows] int32 and n_found [n_rec] int32 from a linkage.  M = the number of leading steps with
+ *   height <= threshold (it stops at the FIRST step above: f32 average linkage may invert by an ulp), at most
+ *   n_r - n_clusters where that is given; leaf i follows `into` while step < M, to its cluster's lowest member; the label
+ *   is the rank of that root among the roots: 0, 1, ... in order of first appearance.  threshold_mode / n_clusters_mode:
+ *   0 not given, 1 the scalar, 2 one value per recording (device vectors); both 0: DS_ERR_UNSUPPORTED. */
+#define DS_AHC_MAX_N 4096
+#define DS_AHC_AVERAGE 0
+#define DS_AHC_COMPLETE 1
+#define DS_AHC_SINGLE 2
+int ds_ahc_plan(const long long *row_off, int n_rec, int D, long long *table, long long *counts);
+long long ds_ahc_workspace_bytes(const long long *row_off, int n_rec);
+int ds_ahc_distances_f32(const float *emb, const long long *table, int n_rec, int n_tiles, int tile_rows, int D,
+                         float *dist, void *stream);
+int ds_ahc_linkage_f32(float *dist, const long long *table, int n_rec, int n_max, int method, int *pair, float *height,
+                       int *size, int *into, int *step, void *stream);
+int ds_ahc_cut(const long long *table, int n_rec, int n_max, const float *height, const int *into, const int *step,
+               const float *threshold_vec, float threshold, int threshold_mode, const int *n_clusters_vec, int n_clusters,
+               int n_clusters_mode, int *labels, int *n_found, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
