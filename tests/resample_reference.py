@@ -54,6 +54,28 @@ def resample(x, L, M, zeros=10, beta=5.0):
     return y
 
 
+def resample_f32(x, L, M, zeros=10, beta=5.0):
+    """The same sum as a float32 kernel has it: float32 samples times the float32-rounded taps, every product and every
+    partial sum rounded to float32, each output summed in the order of ASCENDING input index (tap H + m M - k L falls as
+    k rises, so j runs from the last polyphase tap down).  Its distance from `resample` is what float32 arithmetic costs
+    this operation; it is not claimed bit-equal to the kernel, whose fmaf rounds once per step where this rounds twice.
+    Returns float32."""
+    x = np.asarray(x).astype(np.float32)
+    n = len(x)
+    h = taps(L, M, zeros, beta).astype(np.float32)
+    H = zeros * max(L, M)
+    m = np.arange(n_out(n, L, M), dtype=np.int64)
+    c = H + m * M
+    p, k_hi = c % L, c // L
+    y = np.zeros(len(m), np.float32)
+    for j in range(n_taps(L, M, zeros) - 1, -1, -1):
+        i, k = p + j * L, k_hi - j
+        ok = (i <= 2 * H) & (k >= 0) & (k < n)
+        y[ok] = y[ok] + x[k[ok]] * h[i[ok]]
+    assert y.dtype == np.float32
+    return y
+
+
 def to_float32(x):
     """int16 PCM scaled by 1/32768 (exact in float32); float32 unchanged"""
     x = np.asarray(x)

@@ -87,6 +87,18 @@ def test_values(ctx, rate, dtype):
     B.values(ctx, rate, dtype)
 
 
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("name", sorted(B.GEOMETRY))
+def test_geometry(ctx, name, dtype):
+    B.geometry(ctx, name, dtype)
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("name", B.DIRECT)
+def test_guarded_direct_calls(ctx, name, dtype):
+    B.direct(ctx, name, dtype)
+
+
 def test_identity(ctx):
     B.identity(ctx)
 
@@ -106,6 +118,10 @@ def test_plumbing(ctx):
 @pytest.mark.parametrize("rate", B.E2E_RATES)
 def test_end_to_end_against_float64(ctx, rate):
     B.end_to_end(ctx, rate)
+
+
+def test_end_to_end_to_22050(ctx):
+    B.end_to_end(ctx, *B.E2E_22K)
 
 
 def test_abi_errors(ctx):

@@ -87,6 +87,22 @@ def test_decisions(ctx, kind, dtype):
     B.decisions(ctx, kind, dtype)
 
 
+@pytest.mark.parametrize("conf,kind,dtype", B.ENERGY_CASES)
+def test_energy_values_of_the_table(ctx, conf, kind, dtype):
+    B.energy_values(ctx, kind, dtype, conf)
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("conf", ["16k", "22k"])
+def test_energy_at_a_floor_of_one(ctx, conf, dtype):
+    B.energy_values(ctx, "silence", dtype, conf, floor=1.0)
+
+
+@pytest.mark.parametrize("conf,rule,kind,dtype", B.TABLE_CASES)
+def test_decisions_of_the_table(ctx, conf, rule, kind, dtype):
+    B.decisions(ctx, kind, dtype, conf, rule)
+
+
 def test_clipping_and_isolation(ctx):
     B.clipping(ctx)
 
@@ -98,6 +114,26 @@ def test_selection(ctx):
 @pytest.mark.parametrize("normalize", ["mean", "mean_std"])
 def test_normalisation_over_kept_rows(ctx, normalize):
     B.normalisation(ctx, normalize)
+
+
+@pytest.mark.parametrize("normalize", ["mean", "mean_std", None])
+@pytest.mark.parametrize("conf", B.NORM_CONFS)
+def test_normalisation_across_the_tile_hand_over(ctx, conf, normalize):
+    B.normalisation(ctx, normalize, conf)
+
+
+def test_raw_features_over_kept_rows(ctx):
+    B.normalisation(ctx, None)
+
+
+@pytest.mark.parametrize("dtype", B.DTYPES)
+@pytest.mark.parametrize("conf", ["16k", "22k"])
+def test_guarded_direct_calls(ctx, conf, dtype):
+    B.direct(ctx, conf, dtype, max_frames=1100)
+
+
+def test_chain_from_stereo_44100(ctx):
+    B.chain(ctx)
 
 
 def test_vad_none_is_unchanged(ctx):

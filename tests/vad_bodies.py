@@ -27,20 +27,63 @@ KINDS = ("gated", "ramp") + tuple(PLAIN)
 # Measured worst case over every kind, length and dtype below: host emulator 1.1e-6 ("noise" int16; the host's logf is
 # correctly rounded to within an ulp), MI355X 4.1e-6 ("noise" int16 and "gated" int16; two ulp of the device's logf at
 # |e| >= 16); the frames at the floor ("silence") are exact on both.
-ENERGY_TOL = 1.0001 * (FL + 1) * 2.0 ** -24 + 4 * 2.0 ** -19
-# a decision may differ only where some frame of the window has an energy this close to its threshold: the energy's own
-# band plus the threshold's (|energy_mean_scale| times the mean's error, itself at most ENERGY_TOL)
-BAND = ENERGY_TOL * (1.0 + abs(V.DEFAULTS["energy_mean_scale"]))
-TOL_DB = 5e-4                                    # the filterbank's own bar (tests/test_gpu_fbank.py), same arithmetic
+def energy_tol(frame_len):
+    """the bound above for a frame of `frame_len` samples (frame_len <= 800 keeps |e| < 32: ln(800 * 2^30) = 27.5)"""
+    return 1.0001 * (frame_len + 1) * 2.0 ** -24 + 4 * 2.0 ** -19
+
+
+def band(frame_len, energy_mean_scale):
+    """a decision may differ only where some frame of the window has an energy this close to its threshold: the energy's
+    own band plus the threshold's (|energy_mean_scale| times the mean's error, itself at most the energy's bound)"""
+    return energy_tol(frame_len) * (1.0 + abs(energy_mean_scale))
+
+
+ENERGY_TOL = energy_tol(FL)
+BAND = band(FL, V.DEFAULTS["energy_mean_scale"])
+TOL_DB = 5e-4                                    # the bar the default configuration's features over kept rows had: a ceiling
+GUARD = RB.GUARD
+
+# the frame configurations of fbank_bodies.CONFS the decision runs under (the 32-row tile: 22k, 16k_gaps, 32k_128) ...
+VAD_CONFS = ("16k_odd_len", "22k", "16k_gaps", "8k_abutting", "32k_128", "2k_12", "16k_step1")
+# ... and the rules: name -> (VadConfig keywords, the signals the rule runs on)
+RULES = {
+    "default": ({}, ("gated", "ramp")),
+    "ctx0": (dict(frames_context=0, proportion_threshold=1.0), ("gated", "ramp")),
+    "ctx7": (dict(frames_context=7, proportion_threshold=0.5), ("gated", "ramp")),
+    "ctx64": (dict(frames_context=64, proportion_threshold=0.7), ("gated", "ramp")),      # (0.3 would vote every frame voiced)
+    "ctx33": (dict(frames_context=33, proportion_threshold=0.75), ("gated", "ramp")),
+    "fixed": (dict(energy_mean_scale=0.0, energy_threshold=14.0), ("gated", "ramp")),
+    "falling": (dict(frames_context=1, proportion_threshold=1.0, energy_mean_scale=-0.25, energy_threshold=22.0),
+                ("gated", "ramp")),
+    "floor1": (dict(energy_floor=1.0), ("silence", "gated")),        # silence: ln 1 = 0, exactly
+}
+# every rule under the baseline and under a 32-row configuration, every configuration under the default rule, and the
+# widest halo, an even context, no context and the long odd one once more where the frames are least like the baseline's
+TABLE = tuple([(c, "default") for c in VAD_CONFS] + [
+    ("16k", "ctx0"), ("22k", "ctx0"), ("16k", "ctx7"), ("16k_gaps", "ctx7"), ("16k", "ctx64"), ("32k_128", "ctx64"),
+    ("16k", "ctx33"), ("22k", "ctx33"), ("16k", "fixed"), ("16k_gaps", "fixed"), ("16k", "falling"), ("32k_128", "falling"),
+    ("16k", "floor1"), ("22k", "floor1"),
+    ("2k_12", "ctx64"), ("8k_abutting", "ctx7"), ("16k_step1", "ctx0"), ("16k_odd_len", "ctx33")])
+TABLE_CASES = tuple((c, r, kind, dtype) for c, r in TABLE for kind in RULES[r][1] for dtype in DTYPES)
+ENERGY_CASES = tuple((c, kind, dtype) for c in VAD_CONFS for kind in ("gated", "ramp") for dtype in DTYPES)
+
+
+def conf_of(name):
+    import fbank_bodies as FB
+    return FB.CONFS[name]
+
+
+def rule_kw(rule):
+    return {**V.DEFAULTS, **RULES[rule][0]}
 
 
 def tile_frames(lib):
     return int(lib.raw("ds_vad_tile_frames")())
 
 
-def samples_for(T):
-    """a length that gives T frames, the last one partly zero padding"""
-    return FL // 2 if T == 1 else FL + (T - 1) * FS - 37
+def samples_for(T, fl=FL, fs=FS):
+    """a length that gives T frames, the last one partly zero padding (where the step leaves room for any)"""
+    return fl // 2 if T == 1 else fl + (T - 1) * fs - min(37, fs - 1)
 
 
 def lengths(tile):
@@ -50,9 +93,27 @@ def lengths(tile):
     return ns
 
 
+def frame_counts(tile, tm):
+    """the decision tile's and the filterbank tile's boundaries"""
+    return sorted({1, 2, 3, 63, 64, 65, 129, tile - 1, tile, tile + 1, 2 * tile + 1, tm - 1, tm, tm + 1, 2 * tm + 1})
+
+
+def conf_lengths(tile, c):
+    fl, fs = c.frame_len, c.frame_step
+    return [1, fl - 1, fl + 1] + [samples_for(T, fl, fs) for T in frame_counts(tile, c.tile)]
+
+
+@functools.lru_cache(maxsize=64)
+def _ar(seed, n):
+    """(a sample-by-sample recursion: "gated" and "ramp" of one seed share it)"""
+    x = FR.synthetic_audio(seed, n, kind="ar")
+    x.setflags(write=False)
+    return x
+
+
 def _speech(seed, n):
     rs = np.random.RandomState(seed)
-    return rs, FR.synthetic_audio(seed, n, kind="ar").astype(np.float64), 1e-3 * rs.randn(n)
+    return rs, _ar(seed, n).astype(np.float64), 1e-3 * rs.randn(n)
 
 
 def gated(seed, n):
@@ -67,17 +128,25 @@ def gated(seed, n):
     return (sp * g + bg).astype(np.float32)
 
 
-def ramp(seed, n):
-    """the same speech-like signal fading linearly from full level into the noise floor"""
+def ramp(seed, n, fade=1.0):
+    """the same speech-like signal fading linearly from full level into the noise floor over the first `fade` of the
+    utterance; the rest is the floor alone"""
     _, sp, bg = _speech(seed, n)
-    return (sp * np.linspace(1.0, 0.0, n) + bg).astype(np.float32)
+    return (sp * np.clip(np.linspace(1.0, 1.0 - 1.0 / fade, n), 0.0, None) + bg).astype(np.float32)
 
 
-def signal(kind, seed, n):
+# The table's "ramp" reaches the floor at 0.7 of the utterance.  Fading over the whole utterance, as the default
+# configuration's cases do, leaves fewer than 2 % of the frames unvoiced under a fixed threshold of 14 (the fade crosses it
+# at 1.5 % of full level), and none at all at step 1, where the last frame of the longest utterance still spans a sixth of
+# the fade: "both decisions occur" would fail on the reference alone.
+TABLE_FADE = 0.7
+
+
+def signal(kind, seed, n, fade=1.0):
     if kind == "gated":
         return gated(seed, n)
     if kind == "ramp":
-        return ramp(seed, n)
+        return ramp(seed, n, fade)
     return FR.synthetic_audio(seed, n, kind=kind)
 
 
@@ -89,13 +158,33 @@ def _float_signals(kind, tile):
 
 
 @functools.lru_cache(maxsize=None)
-def batch(kind, dtype, tile):
+def _conf_signals(kind, tile, conf):
+    """the table's signals of one frame configuration: "gated" and "ramp" from the same seeds"""
+    c = conf_of(conf)
+    seed0 = 6000 + 100 * VAD_CONFS.index(conf) if conf in VAD_CONFS else 6900
+    return [signal(kind, seed0 + i, n, TABLE_FADE) for i, n in enumerate(conf_lengths(tile, c))]
+
+
+@functools.lru_cache(maxsize=None)
+def energies(kind, dtype, tile, conf=None, floor=V.DEFAULTS["energy_floor"]):
+    """(signals, float64 energies) of every length, read-only; conf None: the default configuration's own lengths"""
+    fl, fs = (FL, FS) if conf is None else (conf_of(conf).frame_len, conf_of(conf).frame_step)
+    floats = _float_signals(kind, tile) if conf is None else _conf_signals(kind, tile, conf)
+    xs = [FR.int16_quantised(x) if dtype == "int16" else x for x in floats]
+    es = [V.log_energy(x, fl, fs, floor) for x in xs]
+    for a in xs + es:
+        a.setflags(write=False)
+    return xs, es
+
+
+@functools.lru_cache(maxsize=None)
+def batch(kind, dtype, tile, conf=None, rule="default"):
     """(signals, float64 energies, thresholds, reference masks) of every length, read-only"""
-    xs = [FR.int16_quantised(x) if dtype == "int16" else x for x in _float_signals(kind, tile)]
-    es = [V.log_energy(x) for x in xs]
-    thrs = [V.threshold(e) for e in es]
-    masks = [V.decide(e) for e in es]
-    for a in xs + es + masks:
+    kw = rule_kw(rule)
+    xs, es = energies(kind, dtype, tile, conf, kw["energy_floor"])
+    thrs = [V.threshold(e, **kw) for e in es]
+    masks = [V.decide(e, **kw) for e in es]
+    for a in masks:
         a.setflags(write=False)
     return xs, es, thrs, masks
 
@@ -118,29 +207,57 @@ def exempt_frames(e, thr, ctx=CTX, band=BAND):
 
 
 # ---- 1. energy values ----
-def energy_values(ctx, kind, dtype):
+def planned_tile(ctx, c):
+    """the filterbank tile ds_fbank_plan gives the configuration, which the table of cases states too"""
+    import fbank_bodies as FB
+    rc, counts = FB.plan_counts(ctx.lib, [1], c.frame_len, c.frame_step, c.nfft, c.nfilt)
+    assert rc == 0 and counts[2] == c.tile, (counts, c.tile)
+    return counts[2]
+
+
+def energy_values(ctx, kind, dtype, conf=None, floor=None):
+    F = ctx.features
     tile = tile_frames(ctx.lib)
-    xs, es, _, _ = batch(kind, dtype, tile)
-    out, off = ctx.features.frame_log_energy([ctx.t(x) for x in xs])
+    if conf is None:
+        fl, fs, name, config, floor_kw = FL, FS, "", F.FbankConfig(), {}
+        xs, es = energies(kind, dtype, tile, None, V.DEFAULTS["energy_floor"])
+        want = {1, 2, 3, CTX, CTX + 1, 2 * CTX + 1, 63, 64, 65, 129, tile - 1, tile, tile + 1, 2 * tile + 1}
+    else:
+        c = conf_of(conf)
+        fl, fs, name, config = c.frame_len, c.frame_step, f" {conf} {c.frame_len}/{c.frame_step} tile {c.tile}", c.config(F)
+        floor_kw = {} if floor is None else dict(energy_floor=floor)
+        assert (config.frame_len, config.frame_step) == (fl, fs) and fl <= 800
+        xs, es = energies(kind, dtype, tile, conf, V.DEFAULTS["energy_floor"] if floor is None else floor)
+        want = set(frame_counts(tile, planned_tile(ctx, c)))
+    out, off = F.frame_log_energy([ctx.t(x) for x in xs], config, **floor_kw)
     assert out.dtype == torch.float32 and out.dim() == 1 and off.dtype == np.int64
-    assert np.diff(off).tolist() == [len(e) for e in es] == [FR.n_frames(len(x), FL, FS) for x in xs]
-    assert {1, 2, 3, CTX, CTX + 1, 2 * CTX + 1, 63, 64, 65, 129, tile - 1, tile, tile + 1, 2 * tile + 1} <= set(np.diff(off))
+    assert np.diff(off).tolist() == [len(e) for e in es] == [FR.n_frames(len(x), fl, fs) for x in xs]
+    assert want <= set(np.diff(off))
     got = split(out, off)
     err = max(float(np.abs(g - e).max()) for g, e in zip(got, es))
-    print(f"log energy {kind} {dtype}: max abs error {err:.3e}, bound {ENERGY_TOL:.3e}")
-    assert err <= ENERGY_TOL, (err, ENERGY_TOL)
+    tol = energy_tol(fl)
+    print(f"log energy{name} {kind} {dtype}: max abs error {err:.3e}, bound {tol:.3e}")
+    assert err <= tol, (err, tol)
     assert max(float(np.abs(e).max()) for e in es) < 32.0            # the range the bound was derived for
     if kind == "silence":                                            # at the floor: the floor's own logarithm, exactly
         for g, e in zip(got, es):
             np.testing.assert_array_equal(bits(g), bits(e.astype(np.float32)))
+            assert floor is None or (e == np.log(floor)).all()
 
 
 # ---- 2. decisions ----
-def decisions(ctx, kind, dtype):
+def decisions(ctx, kind, dtype, conf=None, rule="default"):
+    F = ctx.features
     tile = tile_frames(ctx.lib)
-    xs, es, thrs, masks = batch(kind, dtype, tile)
+    kw = rule_kw(rule)
+    if conf is None:
+        fl, name, config = FL, "", F.FbankConfig()
+    else:
+        c = conf_of(conf)
+        fl, name, config = c.frame_len, f" {conf} {c.frame_len}/{c.frame_step} tile {planned_tile(ctx, c)} {rule}", c.config(F)
+    xs, es, thrs, masks = batch(kind, dtype, tile, conf, rule)
     # the reference side first: the inputs must leave (next to) nothing to the band
-    exempt = [exempt_frames(e, thr) for e, thr in zip(es, thrs)]
+    exempt = [exempt_frames(e, thr, kw["frames_context"], band(fl, kw["energy_mean_scale"])) for e, thr in zip(es, thrs)]
     n_exempt, n_all = sum(int(x.sum()) for x in exempt), sum(len(x) for x in exempt)
     assert n_exempt <= 0.01 * n_all, (kind, n_exempt, n_all)
     if kind != "ramp":
@@ -150,13 +267,13 @@ def decisions(ctx, kind, dtype):
     else:
         long_ones = np.concatenate([m for m in masks if len(m) >= 63])
         assert 0.02 < long_ones.mean() < 0.98, (kind, long_ones.mean())   # both decisions occur
-    mask, off = ctx.features.voiced_frames([ctx.t(x) for x in xs])
+    mask, off = F.voiced_frames([ctx.t(x) for x in xs], F.VadConfig(**kw), config)
     assert mask.dtype == torch.uint8 and mask.dim() == 1 and np.diff(off).tolist() == [len(m) for m in masks]
     bad = 0
     for g, m, x in zip(split(mask, off), masks, exempt):
         assert set(np.unique(g).tolist()) <= {0, 1}
         bad += int(((g != 0) != m)[~x].sum())
-    print(f"decisions {kind} {dtype}: {n_all} frames, {n_exempt} exempt, {bad} wrong, "
+    print(f"decisions{name} {kind} {dtype}: {n_all} frames, {n_exempt} exempt, {bad} wrong, "
           f"{sum(int(m.sum()) for m in masks) / n_all:.1%} voiced")
     assert bad == 0
 
@@ -197,6 +314,22 @@ def clipping(ctx):
         kept, new_off = F.select_frames(feats, off, mask)
         assert np.diff(new_off).tolist() == [int(m.sum()) for m in ms]
         assert new_off[6] == new_off[5] and new_off[8] == new_off[7] and kept.shape[0] == new_off[-1]
+    # the widest halo: one loud frame is one vote in a window of up to 129, so at 0.01 it lights the frames whose clipped
+    # window holds it and has at most 100 frames.  20 frames: every window is the utterance.  1025 frames: the loud last
+    # frame is alone in the second decision tile and lights 35 frames of the first through that tile's upper halo; its
+    # own window reaches 64 frames back into the first tile
+    cfg = F.VadConfig(frames_context=64, proportion_threshold=0.01)
+    kw = dict(frames_context=64, proportion_threshold=0.01)
+    assert tile_frames(ctx.lib) == 1024
+    for T in (20, 1025):
+        first, last = _one_loud_frame(T, False), _one_loud_frame(T, True)
+        lit = np.array([t <= 64 and min(T - 1, t + 64) + 1 <= 100 for t in range(T)])
+        assert lit.sum() == (20 if T == 20 else 36)
+        assert V.vad(first, **kw).tolist() == lit.tolist() and V.vad(last, **kw).tolist() == lit[::-1].tolist()
+        mask, off = F.voiced_frames([ctx.t(x) for x in (loud, first, loud, last, loud)], cfg)
+        ms = split(mask, off)
+        assert ms[1].tolist() == lit.astype(np.uint8).tolist() and ms[3].tolist() == lit[::-1].astype(np.uint8).tolist()
+        assert all(m.all() for m in ms[0::2])
 
 
 # ---- 4. selection ----
@@ -232,6 +365,13 @@ def selection(ctx):
     m = mask.cpu().numpy().astype(bool)
     np.testing.assert_array_equal(out.cpu().numpy(), rows[m])
     assert np.diff(new_off).tolist() == [int(m[off[u]:off[u + 1]].sum()) for u in range(len(sig))]
+    # every row width the selection is used with (nfilt 4, 12, 64, 128): 1, 3, 16 and 32 vectors per row
+    for width in (4, 12, 64, 128):
+        wide = np.arange(off[-1] * width, dtype=np.float32).reshape(-1, width)
+        assert wide[-1, -1] < 2.0 ** 24                              # the entries name their row exactly
+        out, new_off_w = F.select_frames(ctx.t(wide), off, mask)
+        np.testing.assert_array_equal(out.cpu().numpy(), wide[m])
+        assert new_off_w.tolist() == new_off.tolist()
     # a mask of the caller's own: any non-zero byte keeps the row
     own = np.random.RandomState(3).randint(0, 3, off[-1]).astype(np.uint8) * 127
     out, new_off = F.select_frames(ctx.t(rows), off, ctx.t(own))
@@ -249,34 +389,274 @@ def selection(ctx):
 
 
 # ---- 5. normalisation over the kept rows ----
-@functools.lru_cache(maxsize=None)
-def normalisation_case():
-    xs = [gated(700, 16000), gated(701, 48000), np.zeros(3000, np.float32), gated(702, 5000),
-          FR.synthetic_audio(703, 561, kind="noise"), FR.synthetic_audio(704, 400, kind="tone"),
-          FR.int16_quantised(gated(705, 16000))]
-    masks = [V.vad(x) for x in xs]
-    raw = [FR.fbank(x.astype(np.float32) / np.float32(32768) if x.dtype == np.int16 else x)[m] for x, m in zip(xs, masks)]
-    # the inputs leave nothing to the band, so the reference mask IS the mask
-    assert not any(exempt_frames(V.log_energy(x), V.threshold(V.log_energy(x))).any() for x in xs)
-    assert [len(r) for r in raw][2] == 0 and min(len(r) for i, r in enumerate(raw) if i != 2) >= 1
-    for a in xs + raw:
+NORM_CONFS = ("22k", "16k_gaps", "32k_128", "2k_12")                 # 32-row tiles handed over to the selection's 64; nfilt 128, 12
+KEPT_COUNTS = (0, 1, 63, 64, 65, 129)                                # around the selection's tile of 64 rows
+
+
+def burst(seed, n_loud, n):
+    """speech-like for the first n_loud samples, then the noise floor"""
+    x = 1e-3 * np.random.RandomState(seed).randn(n)
+    x[:n_loud] += _ar(seed, n)[:n_loud]
+    return x.astype(np.float32)
+
+
+def kept_exactly(seed, K, fl, fs):
+    """an utterance of which the default rule keeps exactly K frames (asserted on the restatement): silence for none, one
+    loud frame for one, else a burst at the start whose length is searched in quarter steps, before as many frames of
+    floor again (at least 20), so that the threshold lies between the two levels"""
+    if K == 0:
+        return np.zeros(fl + 3 * fs, np.float32)
+    if K == 1:
+        return _ar(seed, fl // 2).copy()
+    n = samples_for(2 * K + 20, fl, fs)
+    for n_loud in range(max(1, K - 6) * fs, (K + 6) * fs, max(1, fs // 4)):
+        x = burst(seed, n_loud, n)
+        if int(V.vad(x, fl, fs).sum()) == K:
+            return x
+    raise AssertionError(("no burst keeps", K, fl, fs))
+
+
+def mode_name(normalize):
+    return "log" if normalize is None else normalize
+
+
+def normalised(raw, normalize):
+    return raw if normalize is None else FR.normalize_frames(raw, scale=normalize == "mean_std")
+
+
+def kept_references(xs, kw, fl, fs):
+    """(reference masks, float64 log filterbank over the kept rows, the float32 restatement's), asserting that the inputs
+    leave nothing to the band, so that the reference mask IS the mask"""
+    import fbank_bodies as FB
+    masks = [V.vad(x, fl, fs) for x in xs]
+    es = [V.log_energy(x, fl, fs) for x in xs]
+    assert not any(exempt_frames(e, V.threshold(e), CTX, band(fl, V.DEFAULTS["energy_mean_scale"])).any() for e in es)
+    raw = [FR.fbank(FB.as_float(x), **kw)[m] for x, m in zip(xs, masks)]
+    raw32 = [FR.mk_mfb_f32(FB.as_float(x), normalize=None, **kw)[m] for x, m in zip(xs, masks)]
+    for a in raw + raw32:
         a.setflags(write=False)
-    return xs, raw
+    return masks, raw, raw32
 
 
-def normalisation(ctx, normalize):
+@functools.lru_cache(maxsize=None)
+def normalisation_case(conf=None):
+    """(signals, the float32 ones first, how many those are, kept rows in float64, kept rows of the float32 restatement)"""
+    if conf is None:
+        xs = [gated(700, 16000), gated(701, 48000), np.zeros(3000, np.float32), gated(702, 5000),
+              FR.synthetic_audio(703, 561, kind="noise"), FR.synthetic_audio(704, 400, kind="tone"),
+              FR.int16_quantised(gated(705, 16000))]
+        n_float = 6
+        _, raw, raw32 = kept_references(xs, {}, FL, FS)
+        assert [len(r) for r in raw][2] == 0 and min(len(r) for i, r in enumerate(raw) if i != 2) >= 1
+    else:
+        c = conf_of(conf)
+        fl, fs = c.frame_len, c.frame_step
+        xs = [kept_exactly(7100 + 10 * NORM_CONFS.index(conf) + i, K, fl, fs) for i, K in enumerate(KEPT_COUNTS)]
+        n_float = len(xs)
+        xs += [FR.int16_quantised(x) for x in xs[3:5]]               # int16 copies of the 64 and the 65
+        _, raw, raw32 = kept_references(xs, c.ref_kw(), fl, fs)
+        assert [len(r) for r in raw] == list(KEPT_COUNTS) + [64, 65]
+    for x in xs:
+        x.setflags(write=False)
+    return xs, n_float, raw, raw32
+
+
+def normalisation(ctx, normalize, conf=None):
+    """features over the voiced frames, normalised over what was kept, against the float64 chain under the filterbank's
+    restated bar for the configuration and mode: max(floor, 4 x the float32 restatement's distance), over the kept rows"""
+    import fbank_bodies as FB
     F = ctx.features
-    xs, raw = normalisation_case()
-    worst = 0.0
-    for sel in (slice(0, 6), slice(6, 7)):                           # the float32 utterances, then the int16 one
-        out, off = F.log_mel_fbank([ctx.t(x) for x in xs[sel]], normalize=normalize, vad=F.VadConfig())
-        assert np.diff(off).tolist() == [len(r) for r in raw[sel]] and out.shape == (off[-1], 64)
-        for g, r in zip(split(out, off), raw[sel]):
+    xs, n_float, raw, raw32 = normalisation_case(conf)
+    config = F.FbankConfig() if conf is None else conf_of(conf).config(F)
+    if conf is not None:
+        assert planned_tile(ctx, conf_of(conf)) == conf_of(conf).tile
+    metric, floor = FB.METRIC[mode_name(normalize)]
+    worst = restated = 0.0
+    for sel in (slice(0, n_float), slice(n_float, len(xs))):         # the float32 utterances, then the int16 ones
+        out, off = F.log_mel_fbank([ctx.t(x) for x in xs[sel]], config, normalize=normalize, vad=F.VadConfig())
+        assert np.diff(off).tolist() == [len(r) for r in raw[sel]] and out.shape == (off[-1], config.nfilt)
+        for g, r, r32 in zip(split(out, off), raw[sel], raw32[sel]):
             if len(r):
-                ref = r if normalize is None else FR.normalize_frames(r, scale=normalize == "mean_std")
-                worst = max(worst, float(np.abs(g - ref).max()))
-    print(f"fbank over voiced frames, normalize={normalize}: max abs error {worst:.3e}")
-    assert worst <= TOL_DB, worst
+                ref = normalised(r, normalize)
+                assert normalize == "mean_std" or np.abs(ref).max() < 128.0       # FLOOR_DB is one ulp there
+                worst = max(worst, metric(g, ref))
+                restated = max(restated, metric(normalised(r32.astype(np.float64), normalize).astype(np.float32), ref))
+    bar = FB.bar_from_restatement(floor, restated)
+    if conf is None:
+        bar = min(bar, TOL_DB)                                       # never looser than the bar this case had
+    FB.say(f"fbank over voiced frames {conf or 'default'}", mode_name(normalize), restated, bar, worst)
+    assert worst <= bar, (conf, normalize, worst, bar)
+    assert conf is not None or worst <= TOL_DB, worst
+
+
+# ---- 5a. the entry points on guarded buffers ----
+FILL = 0xAA                                      # every byte of a buffer a kernel is to write: no count, scan or 0 / 1 looks so
+
+
+class Guarded:
+    """A device buffer of n entries whose every byte is FILL (float: NaN), between GUARD entries of the same on both sides;
+    `inside` is what the kernel is handed."""
+
+    def __init__(self, ctx, n, dtype):
+        self.n, self.dtype = n, dtype
+        self.floating = dtype in (torch.float32, torch.float64)
+        width = torch.empty(0, dtype=dtype).element_size()
+        if self.floating:
+            self.buf = torch.full((n + 2 * GUARD,), float("nan"), dtype=dtype, device=ctx.dev)
+        else:
+            self.buf = torch.full(((n + 2 * GUARD) * width,), FILL, dtype=torch.uint8, device=ctx.dev).view(dtype)
+        self.inside = self.buf[GUARD:GUARD + n]
+        self.fill = None if self.floating else np.full(width, FILL, np.uint8).view(self.buf.cpu().numpy().dtype)[0]
+
+    def untouched(self, a):
+        return np.isnan(a) if self.floating else a == self.fill
+
+    def read(self, what, written=None):
+        """the inside on the host: both guards as they were, every entry (of the first `written`) overwritten"""
+        a = self.buf.cpu().numpy()
+        assert self.untouched(a[:GUARD]).all(), f"{what}: a store before the buffer"
+        assert self.untouched(a[GUARD + self.n:]).all(), f"{what}: a store past the buffer"
+        got = a[GUARD:GUARD + self.n]
+        assert not self.untouched(got[:self.n if written is None else written]).any(), f"{what}: an entry was not written"
+        return got.copy()
+
+
+def direct(ctx, conf, dtype, max_frames=None):
+    """ds_vad_log_energy_f32, ds_vad_decide, ds_vad_scan and ds_vad_select_f32 called as features.py calls them, on buffers
+    that show a read past the samples or a store outside any output; the results are the public functions' bits.
+    `max_frames`: leave out the longer utterances (the host emulator's filterbank is slow)"""
+    import fbank_bodies as FB
+    F, lib = ctx.features, ctx.lib
+    eng = F._eng()
+    c = conf_of(conf)
+    config, vad = c.config(F), F.VadConfig()
+    fl, fs, nfilt = c.frame_len, c.frame_step, c.nfilt
+    tile = tile_frames(lib)
+    xs = [x for x in energies("gated", dtype, tile, conf, V.DEFAULTS["energy_floor"])[0]
+          if max_frames is None or FR.n_frames(len(x), fl, fs) <= max_frames]
+    assert max(FR.n_frames(len(x), fl, fs) for x in xs) > tile       # more than one decision tile
+    xs = xs[:3] + [np.zeros(fl + 5 * fs, xs[0].dtype)] + xs[3:]      # an utterance without a kept row among the others
+    n_utt, lens = len(xs), np.array([len(x) for x in xs], np.int64)
+    int16 = xs[0].dtype == np.int16
+    tail = np.full(GUARD, -32768, np.int16) if int16 else np.full(GUARD, np.nan, np.float32)
+    samples = ctx.t(np.concatenate(list(xs) + [tail]))
+    # the filterbank's table
+    rc, (n_frames, n_tiles, tm) = FB.plan_counts(lib, lens, fl, fs, c.nfft, nfilt)
+    assert rc == 0 and tm == c.tile
+    table = np.full(3 * (n_utt + 1) + n_tiles, -7, np.int64)
+    assert FB.plan_counts(lib, lens, fl, fs, c.nfft, nfilt, table) == (0, [n_frames, n_tiles, tm])
+    offsets = table[n_utt + 1:2 * (n_utt + 1)].copy()
+    table_dev = ctx.t(table)
+    # energies
+    energy = Guarded(ctx, n_frames, torch.float32)
+    eng.lib.call("ds_vad_log_energy_f32", eng._p(samples), int(int16), eng._p(table_dev), n_utt, n_tiles, tm, fl, fs,
+                 float(vad.energy_floor), eng._p(energy.inside), eng._stream(energy.buf))
+    e = energy.read("energy")
+    # the decision
+    counts = np.zeros(3, np.int64)
+    assert lib.raw("ds_vad_plan")(offsets.ctypes.data, n_utt, None, counts.ctypes.data) == 0
+    n_dtiles = int(counts[1])
+    vtable = np.full(2 * (n_utt + 1) + n_dtiles, -7, np.int64)
+    assert lib.raw("ds_vad_plan")(offsets.ctypes.data, n_utt, vtable.ctypes.data, counts.ctypes.data) == 0
+    assert counts.tolist() == [n_frames, n_dtiles, tile] and (vtable != -7).all()
+    vtable_dev = ctx.t(vtable)
+    n_ws = int(lib.raw("ds_vad_workspace_bytes")(n_utt, n_dtiles)) // 8
+    assert n_ws == n_utt + n_dtiles
+
+    def buffers():
+        return (Guarded(ctx, n_frames, torch.int32), Guarded(ctx, n_utt, torch.int64), Guarded(ctx, n_ws, torch.int64))
+
+    mask = Guarded(ctx, n_frames, torch.uint8)
+    scan, kept, ws = buffers()
+    eng.lib.call("ds_vad_decide", eng._p(energy.inside), eng._p(vtable_dev), n_utt, n_dtiles, float(vad.energy_threshold),
+                 float(vad.energy_mean_scale), int(vad.frames_context), float(vad.proportion_threshold),
+                 eng._p(mask.inside), eng._p(scan.inside), eng._p(kept.inside), eng._p(ws.inside), eng._stream(mask.buf))
+    m, sc, kp = mask.read("mask"), scan.read("scan"), kept.read("kept")
+    ws.read("decision workspace")
+    assert set(np.unique(m).tolist()) <= {0, 1}
+    want_scan = np.concatenate([np.cumsum(m[offsets[u]:offsets[u + 1]]) - m[offsets[u]:offsets[u + 1]] for u in range(n_utt)])
+    assert sc.tolist() == want_scan.tolist()
+    assert kp.tolist() == [int(m[offsets[u]:offsets[u + 1]].sum()) for u in range(n_utt)] and kp[3] == 0 and kp.sum() > 100
+    # the scan of a mask, alone: the same scan and counts
+    scan2, kept2, ws2 = buffers()
+    eng.lib.call("ds_vad_scan", eng._p(mask.inside), eng._p(vtable_dev), n_utt, n_dtiles, eng._p(scan2.inside),
+                 eng._p(kept2.inside), eng._p(ws2.inside), eng._stream(mask.buf))
+    assert scan2.read("scan alone").tolist() == sc.tolist() and kept2.read("kept alone").tolist() == kp.tolist()
+    counts2 = ws2.read("scan workspace", written=0)[n_utt:]          # (the thresholds' part is the decision's alone)
+    assert (counts2 >= 0).all(), "a tile's count was not written"
+    assert mask.read("mask after the scan").tolist() == m.tolist()
+    # the selection, of the public call's log features
+    feats, off = F.log_mel_fbank([ctx.t(x) for x in xs], config, normalize=None)
+    assert off.tolist() == offsets.tolist()
+    k_tiles = -(-kp // F.SELECT_TILE_ROWS)
+    n_ktiles, n_kept = int(k_tiles.sum()), int(kp.sum())
+    ktable_dev = ctx.t(F._ragged_table([np.zeros(n_utt, np.int64), kp], k_tiles))
+    n_stats = int(lib.raw("ds_fbank_workspace_bytes")(n_utt, n_ktiles, nfilt)) // 8
+    rows, stats = Guarded(ctx, n_kept * nfilt, torch.float32), Guarded(ctx, n_stats, torch.float64)
+    eng.lib.call("ds_vad_select_f32", eng._p(feats), eng._p(mask.inside), eng._p(scan.inside), eng._p(vtable_dev),
+                 eng._p(ktable_dev), n_utt, n_ktiles, nfilt, F.SELECT_TILE_ROWS, eng._p(rows.inside), eng._p(stats.inside),
+                 eng._stream(rows.buf))
+    sel = rows.read("selected rows").reshape(n_kept, nfilt)
+    part = stats.read("the tiles' statistics", written=2 * nfilt * n_ktiles)
+    np.testing.assert_array_equal(bits(sel), bits(feats.cpu().numpy()[m != 0]))
+    # a tile's sums are those of its rows: {sum, sum of squares} per filter, 64 rows of one utterance per tile
+    koff = np.concatenate([[0], np.cumsum(kp)])
+    first = [koff[u] + 64 * j for u in range(n_utt) for j in range(k_tiles[u])]
+    last = [min(koff[u] + 64 * (j + 1), koff[u + 1]) for u in range(n_utt) for j in range(k_tiles[u])]
+    sums = np.array([[sel[a:b].astype(np.float64).sum(0), (sel[a:b].astype(np.float64) ** 2).sum(0)] for a, b in zip(first, last)])
+    np.testing.assert_allclose(part[:2 * nfilt * n_ktiles].reshape(n_ktiles, 2, nfilt), sums, rtol=1e-12, atol=1e-9)
+    # the public functions: the same bits
+    pe, poff = F.frame_log_energy([ctx.t(x) for x in xs], config)
+    pm, _ = F.voiced_frames([ctx.t(x) for x in xs], vad, config)
+    ps, pnew = F.select_frames(feats, off, pm)
+    pf, pfo = F.log_mel_fbank([ctx.t(x) for x in xs], config, normalize=None, vad=vad)
+    assert poff.tolist() == offsets.tolist() and pnew.tolist() == koff.tolist() == pfo.tolist()
+    np.testing.assert_array_equal(bits(pe.cpu().numpy()), bits(e))
+    assert pm.cpu().numpy().tolist() == m.tolist()
+    np.testing.assert_array_equal(bits(ps.cpu().numpy()), bits(sel))
+    np.testing.assert_array_equal(bits(pf.cpu().numpy()), bits(sel))
+    print(f"vad direct {conf} {dtype}: {n_frames} frames in {n_tiles} tiles of {tm}, {n_dtiles} decision tiles, "
+          f"{n_kept} kept rows of {nfilt} in {n_ktiles} tiles")
+
+
+# ---- 5b. the chain ----
+@functools.lru_cache(maxsize=None)
+def chain_case():
+    """1.5 s of stereo int16 at 44100 Hz and its float64 chain under fbank_bodies.CONFS["22k"]: down-mix -> resample ->
+    decision -> filterbank over the kept rows; the float32 restatements of the resampler and the filterbank for the bar"""
+    import resample_reference as R
+    c = conf_of("22k")
+    fl, fs = c.frame_len, c.frame_step
+    rule = RULES["ctx7"][0]
+    n = 66150
+    g = gated(7300, n)
+    stereo = FR.int16_quantised(np.stack([g, 0.5 * g], 1).reshape(-1))
+    mono = R.downmix(stereo, 2)
+    y = R.resample(mono, 1, 2).astype(np.float32)
+    e = V.log_energy(y, fl, fs)
+    m = V.decide(e, **{**V.DEFAULTS, **rule})
+    assert not exempt_frames(e, V.threshold(e), rule["frames_context"], band(fl, V.DEFAULTS["energy_mean_scale"])).any()
+    assert 0.1 < m.mean() < 0.9
+    raw = FR.fbank(y, **c.ref_kw())[m]
+    raw32 = FR.mk_mfb_f32(R.resample_f32(mono, 1, 2), normalize=None, **c.ref_kw())[m]
+    for a in (stereo, raw, raw32):
+        a.setflags(write=False)
+    return stereo, raw, raw32
+
+
+def chain(ctx):
+    import fbank_bodies as FB
+    F = ctx.features
+    stereo, raw, raw32 = chain_case()
+    out, off = F.log_mel_fbank([ctx.t(stereo)], conf_of("22k").config(F), orig_rate=44100, channels=2,
+                               vad=F.VadConfig(**RULES["ctx7"][0]), normalize="mean_std")
+    assert off.tolist() == [0, len(raw)] and out.shape == (len(raw), 64)
+    metric, floor = FB.METRIC["mean_std"]
+    ref = normalised(raw, "mean_std")
+    restated = metric(normalised(raw32.astype(np.float64), "mean_std").astype(np.float32), ref)
+    bar, err = FB.bar_from_restatement(floor, restated), metric(out.cpu().numpy(), ref)
+    FB.say(f"44100 Hz stereo int16 -> 22050 -> vad -> fbank, {len(raw)} kept rows", "mean_std", restated, bar, err)
+    assert err <= bar, (err, bar)
 
 
 def vad_none_is_unchanged(ctx):
